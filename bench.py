@@ -16,16 +16,23 @@ equal --gpus or the bench exits with status 2.  value = all ranks' input pixels 
 max-over-ranks wall time of K steps.  Every timed step, at every N including N = 1 (a
 world-1 process group), ends with per-image, per-channel sums of a row sample of its output
 (every 256th row) all-gathered over RCCL (the collective stays inside the timed
-loop; a few KB per rank), so the per-step work is the same at every N.  After the timed
-region, full per-image checksums are all-gathered, and (N>1) the full-output gather to
-rank 0 is timed and reported on its own (`gather`), never folded into `value`.
+loop; a few KB per rank), so the per-step work is the same at every N.
+
+A plain run sets up, pre-warms, warms up, times the K steps, writes its outputs if
+`--dump-outputs DIR` is given (what the last timed step returned, float32, see dump_outputs)
+and prints the line.  `--full` adds everything that takes runs of its own, each reported
+beside `value` and never folded into it: the secondary lines (`unfused`, `roundtrip`,
+`pyramid`, `wide_conv`, `lattices`), `cpu_baseline`, the full per-image checksums
+all-gathered after the timed region (`checksum`), and (N>1) the timed full-output gather to
+rank 0 (`gather`).  Without `--full` those fields are null.
 `--dry-run`: the same launch, process groups (gloo), barriers, per-step collective,
 max-over-ranks timing and JSON line on the CPU with a stand-in step and no HIP kernel
 (tests/test_bench_launch.py); its value is not a measurement.
 
 Extra JSON fields: `kernels` (per-stage HIP-event times and algorithmic GB/s),
-`roofline` (dominant kernel vs 8 TB/s HBM), `cpu_baseline` (the C/OpenMP oracle
-restatement on a bounded sample, rank 0 at N=1 only).
+`roofline` (dominant kernel vs 8 TB/s HBM), both from the HIP events of the timed steps;
+with `--full`, `cpu_baseline` (the C/OpenMP oracle restatement on a bounded sample, rank 0
+at N=1 only).
 """
 import argparse
 import json
@@ -102,7 +109,50 @@ def parse():
                          "collective, timing and JSON line with a CPU stand-in step (tests)")
     ap.add_argument("--pmc-json", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"),
                     help="per-kernel HBM bytes from rocprofv3 PMC passes (optional)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything that takes runs of its own: the "
+                         "secondary lines (unfused, roundtrip, pyramid, wide_conv, lattices), the "
+                         "CPU baseline, the output checksums and (N > 1) the timed output gather; "
+                         "the --no-* options and --cpu-images pick among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to "
+                         "DIR/output.npy (float32; rank r > 0: output_rank<r>.npy): the whole "
+                         "tensor, or whole rows of it picked with a fixed seed when it is larger "
+                         "than 32 MB, their row numbers in DIR/output_rows.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        # a plain run does what the headline needs and nothing else
+        args.no_compare = args.no_pyramid = args.no_roundtrip = True
+        args.no_wide_conv = args.no_lattices = args.no_gather = True
+        args.cpu_images = 0
+    return args
+
+
+DUMP_SAMPLE_BYTES = 32 << 20
+
+
+def dump_outputs(path, y, name):
+    """--dump-outputs: y as float32 in path/name.npy.  A tensor above DUMP_SAMPLE_BYTES (as
+    float32) is sampled: whole rows of its (rows, W) view, always the first and last one, the
+    rest drawn with a fixed seed from the shape alone, so two builds run with the same arguments
+    write the same rows; path/name_rows.npy (float64) holds their row numbers."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    w = int(y.shape[-1])
+    flat = y.reshape(-1, w)
+    rows = int(flat.shape[0])
+    keep = max(2, DUMP_SAMPLE_BYTES // (4 * w))
+    if rows > keep:
+        pick = np.random.default_rng(0).choice(rows - 2, size=keep - 2, replace=False) + 1
+        pick = np.sort(np.concatenate([[0], pick, [rows - 1]])).astype(np.int64)
+        out = flat[torch.from_numpy(pick).to(flat.device)]
+    else:
+        pick = np.arange(rows, dtype=np.int64)
+        out = y
+    np.save(os.path.join(path, name + ".npy"), out.to(torch.float32).cpu().numpy())
+    np.save(os.path.join(path, name + "_rows.npy"), pick.astype(np.float64))
 
 
 def cpu_model():
@@ -492,6 +542,8 @@ def main():
         stages = ("pipeline_r2h_conv_h2r",)
         y, elapsed, sms = measure(run_fused, args.steps, args.warmup)
     stage_ms = dict(zip(stages, sms))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, y, "output" if rank == 0 else f"output_rank{rank}")
     ms_per_step = elapsed / args.steps * 1e3
     mpix = world * B * H * W * args.steps / elapsed / 1e6
     alg_bytes = {s: 2 * img_bytes for s in stages}   # each kernel: read once + write once
@@ -786,12 +838,13 @@ def main():
     if not args.unfused and not dry and not args.no_lattices:
         lattices = bench_lattices(ops, measure_line, gen, dev, world, args.lattice_batch, C, H, W)
 
-    # checksums over RCCL (not timed), and the full-output gather on its own
+    # --full: checksums over RCCL (not timed), and the full-output gather on its own
     from HyGrid.dist import gather_checksums, gather_to_root, image_checksums
-    cs = image_checksums(y)
+    cs = image_checksums(y) if args.full else None
     gather = None
     if world > 1:
-        cs = gather_checksums(cs.to(cdev))
+        if args.full:
+            cs = gather_checksums(cs.to(cdev))
         if not args.no_gather and not rehearse and not dry:
             try:
                 gather_to_root(y)            # warm the RCCL channels
@@ -808,7 +861,7 @@ def main():
                           "xgmi_ingress_bound_GB_per_s": round(min(world - 1, 7) * 153.0, 1)}
             except Exception as exc:
                 log("gather failed:", exc)
-    checksum = float(cs[..., 0].sum().item())
+    checksum = float(cs[..., 0].sum().item()) if args.full else None
 
     cpu = None
     if rank == 0 and world == 1 and args.cpu_images > 0 and not dry:
@@ -836,7 +889,7 @@ def main():
             "kernels": kernels, "roofline": roofline, "cpu_baseline": cpu,
             "unfused": compare, "roundtrip": roundtrip, "pyramid": pyramid, "wide_conv": wide,
             "lattices": lattices,
-            "gather": gather, "checksum": checksum,
+            "gather": gather, "checksum": checksum, "full": args.full,
             "device": "cpu (dry run)" if dry else torch.cuda.get_device_name(dev),
         }
         if dry:

@@ -13,11 +13,11 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout
 tail -2 "$OUT/pytest_gpu.log"
 timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" \
     > "$OUT/smoke.log" 2>&1 || { echo "smoke failed"; tail -20 "$OUT/smoke.log"; exit 1; }
-timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" \
+timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" \
     || { echo "bench failed"; tail -30 "$OUT/bench.err"; exit 1; }
 cat "$OUT/bench.json"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
-    python3 bench.py --steps 20 --warmup 5 --cpu-images 0 > "$OUT/prof_bench.json" 2> "$OUT/prof.err" \
+    python3 bench.py --full --steps 20 --warmup 5 --cpu-images 0 > "$OUT/prof_bench.json" 2> "$OUT/prof.err" \
     || { echo "rocprof failed"; tail -30 "$OUT/prof.err"; exit 1; }
 find "$OUT/prof" -name '*kernel_stats.csv' -exec cp {} "$OUT/bench_kernel_stats.csv" \;
 T=$(find "$OUT/prof" -name '*kernel_trace.csv' | head -1)

@@ -6,7 +6,7 @@
 #   "test FILE..."          pytest on those files (verbose tail, per-test timeout)
 #   "gputests"              the whole -m gpu suite
 #   "smoke"                 __graft_entry__.smoke()
-#   "bench [ARGS...]"       bench.py (default: the driver's --steps 20 --warmup 5)
+#   "bench [ARGS...]"       bench.py (default: --full --steps 20 --warmup 5, every secondary line)
 #   "ab TOOL ARGS..."       tools/TOOL.py ARGS (in-process A/B of library variants)
 #   "py SCRIPT ARGS..."     any tools/ python script (prof drivers, microbench drivers)
 #   "sq STAGE BATCH"        SQ counter passes of tools/prof_pipeline.py STAGE (tools/pmc_fused.sh)
@@ -32,7 +32,7 @@ for S in "$@"; do
                >> "$log" 2>&1; rc=$?; tail -3 "$log" ;;
     smoke) timeout -k 10 150 python -u -c "import __graft_entry__ as g; g.smoke()" >> "$log" 2>&1; rc=$?
            tail -2 "$log" ;;
-    bench) [ $# -eq 0 ] && set -- --steps 20 --warmup 5
+    bench) [ $# -eq 0 ] && set -- --full --steps 20 --warmup 5
            timeout -k 10 400 python -u bench.py "$@" > "$OUT/bench_$n.json" 2>> "$log"; rc=$?
            cat "$OUT/bench_$n.json" | tee -a "$log" ;;
     ab)    tool=$1; shift
