@@ -81,6 +81,10 @@ SIGNATURES = {
     "hg_pipeline_r2h_h2r": ([_vp, _vp, _int, _int] + [_i64] * 5 + [_vp], _int),
     "hg_pipeline_r2h_conv_h2r": ([_vp, _vp, _vp, _vp, _int, _int] + [_i64] * 9 +
                                  [_int, _int, _int, _dbl, _vp], _int),
+    "hg_pipeline_r2h_conv_h2r_backward_workspace": ([_int, _int] + [_i64] * 9 +
+                                                    [_int, _int, _int, _dbl], _i64),
+    "hg_pipeline_r2h_conv_h2r_backward": ([_vp] * 6 + [_int, _int] + [_i64] * 9 +
+                                          [_int, _int, _int, _dbl, _vp, _i64, _vp], _int),
 }
 ABI_VERSION = 1
 
@@ -119,7 +123,8 @@ def lib():
 
 def fused_layout(md):
     """(band_rows, window_owned_columns, window_left_halo) of the streaming fused kernel's
-    mode md (0 pipeline, 1 HexConv2d, 2 round trip): where its bands and windows end."""
+    mode md (0 pipeline, 1 HexConv2d, 2 round trip): where its bands and windows end.  md 9:
+    (tile rows, tile columns, tiles per weight-pass band) of the chain's backward passes."""
     rows, own, halo = _int(), _int(), _int()
     check(lib().hg_fused_layout(int(md), ctypes.byref(rows), ctypes.byref(own),
                                 ctypes.byref(halo)), "hg_fused_layout")

@@ -495,6 +495,89 @@ def pipeline_r2h_conv_h2r(x, kernel, bias, hex_size=None, rect_size=None, paddin
     return y
 
 
+def _chain_geometry(x, kernel, hex_size, rect_size, padding):
+    B, C, h, w = (int(s) for s in x.shape)
+    h1, w1 = (h, w) if hex_size is None else (int(hex_size[0]), int(hex_size[1]))
+    ho, wo = hexconv2d_out_shape(h1, w1, 2, 1, padding, 1)
+    h2, w2 = (ho, wo) if rect_size is None else (int(rect_size[0]), int(rect_size[1]))
+    return B, C, int(kernel.shape[0]), h, w, h1, w1, h2, w2
+
+
+def pipeline_r2h_conv_h2r_backward_workspace(x, gy_dtype, kernel, hex_size=None, rect_size=None,
+                                             padding=1, groups=1, even_odd_offset=0,
+                                             padding_value=0.0):
+    """Bytes of workspace the fused backward of pipeline_r2h_conv_h2r needs for the 4-D input x
+    and an upstream gradient of gy_dtype, or None when the backward does not cover the call
+    (hg_pipeline_r2h_conv_h2r_backward_workspace; nothing is launched)."""
+    if x.dim() != 4 or x.dtype not in _abi.TORCH_DTYPE or gy_dtype not in _abi.TORCH_DTYPE:
+        return None
+    try:
+        geo = _chain_geometry(x, kernel, hex_size, rect_size, int(padding))
+    except ValueError:
+        return None
+    B, C, O, h, w, h1, w1, h2, w2 = geo
+    need = int(_abi.lib().hg_pipeline_r2h_conv_h2r_backward_workspace(
+        _abi.dtype_code(x.dtype), _abi.dtype_code(gy_dtype), B, C, O, h, w, h1, w1, h2, w2,
+        int(padding), int(groups), int(even_odd_offset), float(padding_value)))
+    return need if need > 0 else None
+
+
+# one byte workspace per (device, stream) for the fused backward's slab of partial sums (every
+# call writes the rows it reads; calls on one stream are ordered, so they can share it)
+_BWD_WS = {}
+
+
+def _backward_workspace(device, stream, nbytes):
+    key = (device.index, int(stream.value or 0))
+    ws = _BWD_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, device=device)
+        _BWD_WS[key] = ws
+    return ws
+
+
+def pipeline_r2h_conv_h2r_backward(gy, x, kernel, hex_size=None, rect_size=None, padding=1,
+                                   groups=1, even_odd_offset=0, padding_value=0.0, need_x=True,
+                                   need_k=True, need_b=True):
+    """Gradients of pipeline_r2h_conv_h2r (hg_pipeline_r2h_conv_h2r_backward): (d x, d kernel,
+    d bias) for the upstream gradient gy (B, O, h2, w2) and the forward's input x (B, C, h, w),
+    with no hex-sized tensor in memory (the hex image is recomputed on chip).
+
+    d x has x's dtype; d kernel (O, C/groups, 7) and d bias (O,) are float32 and bit-reproducible
+    from call to call.  None for the gradients not requested.  Returns None (not a tuple) when
+    the fused backward does not cover the call; raises on argument errors.
+    """
+    _abi.require_device(gy)
+    x = x.detach().contiguous()
+    gy = gy.detach()
+    if gy.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+        gy = gy.float()
+    gy = gy.contiguous()
+    need = pipeline_r2h_conv_h2r_backward_workspace(x, gy.dtype, kernel, hex_size, rect_size,
+                                                    padding, groups, even_odd_offset,
+                                                    padding_value)
+    if need is None:
+        return None
+    B, C, O, h, w, h1, w1, h2, w2 = _chain_geometry(x, kernel, hex_size, rect_size, int(padding))
+    if tuple(gy.shape) != (B, O, h2, w2):
+        raise ValueError(f"gy has shape {tuple(gy.shape)}, expected {(B, O, h2, w2)}")
+    k = kernel.detach().float().reshape(O, -1).contiguous()
+    dx = torch.empty_like(x) if need_x else None
+    dk = torch.empty((O, k.shape[1] // 7, 7), dtype=torch.float32, device=x.device) if need_k else None
+    db = torch.empty((O,), dtype=torch.float32, device=x.device) if need_b else None
+    st_ = _abi.stream_of(x)
+    ws = _backward_workspace(x.device, st_, need) if (need_k or need_b) else None
+    st = _abi.lib().hg_pipeline_r2h_conv_h2r_backward(
+        _abi.ptr(x), _abi.ptr(k), _abi.ptr(gy), _abi.ptr(dx), _abi.ptr(dk), _abi.ptr(db),
+        _abi.dtype_code(x.dtype), _abi.dtype_code(gy.dtype), B, C, O, h, w, h1, w1, h2, w2,
+        int(padding), int(groups), int(even_odd_offset), float(padding_value), _abi.ptr(ws),
+        ws.numel() if ws is not None else 0, st_)
+    if st == HG_EUNSUP:
+        return None
+    _abi.check(st, "hg_pipeline_r2h_conv_h2r_backward")
+    return dx, dk, db
+
+
 # one int32 workspace per (device, stream) for hg_hex_pyramid_chain (each call zeroes it on the
 # stream first; calls on one stream are ordered, so they can share it)
 _CHAIN_WS = {}

@@ -6,11 +6,14 @@ rect_to_hex_resample (geometry_np.py:358-519) -> HexConvModule / HexConv2d
 (geometry_np.py:191-356).  `rect_hex_conv_rect` runs the fused gfx950 kernel
 (hg_pipeline_r2h_conv_h2r: one read of the input, one write of the output)
 whenever the geometry is near-identity and the layer is a plain radius-2,
-stride-1, constant-padded HexConv2d; otherwise the three HIP operators.
+stride-1, constant-padded HexConv2d; otherwise the three HIP operators.  Under autograd the
+fused pass is differentiated by its own fused backward (hg_pipeline_r2h_conv_h2r_backward,
+_FusedChainFn) wherever that covers the call, so training keeps no hex-sized tensor.
 """
 import os
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import ops
 from .HexFrames import HexConv2d
@@ -27,20 +30,74 @@ def fusable(conv):
             and conv.groups in (1, conv.in_channels) and conv.kernel.dtype == torch.float32)
 
 
+def _FORWARD_PAIR(x_dtype, out_dtype):
+    """An (input, output) dtype pair the fused forward implements for float inputs."""
+    return (out_dtype in (x_dtype, torch.float32)
+            or (x_dtype, out_dtype) == (torch.float32, torch.bfloat16))
+
+
+class _FusedChainFn(torch.autograd.Function):
+    """The fused chain under autograd: forward = hg_pipeline_r2h_conv_h2r, backward =
+    hg_pipeline_r2h_conv_h2r_backward.  Only x, the kernel and the geometry are saved: the hex
+    image is recomputed on chip in the backward, so no hex-sized tensor is kept."""
+
+    @staticmethod
+    def forward(ctx, x, kernel, bias, geom, out_dtype):
+        y = ops.pipeline_r2h_conv_h2r(x, kernel, bias, *geom, out_dtype)
+        if y is None:
+            raise RuntimeError("rect_hex_conv_rect: the fused forward refused a call its "
+                               "backward covers")
+        ctx.geom = geom
+        ctx.bias_dtype = bias.dtype if bias is not None else None
+        ctx.save_for_backward(x, kernel)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, kernel = ctx.saved_tensors
+        need_x, need_k, need_b = ctx.needs_input_grad[:3]
+        need_b = need_b and ctx.bias_dtype is not None
+        out = ops.pipeline_r2h_conv_h2r_backward(gy, x, kernel, *ctx.geom, need_x=need_x,
+                                                 need_k=need_k, need_b=need_b)
+        if out is None:
+            raise RuntimeError("rect_hex_conv_rect: the fused backward refused a call its "
+                               "workspace query covered")
+        dx, dk, db = out
+        if dk is not None:
+            dk = dk.reshape(kernel.shape).to(kernel.dtype)
+        if db is not None:
+            db = db.to(ctx.bias_dtype)
+        return dx, dk, db, None, None
+
+
 def rect_hex_conv_rect(x, conv, hex_size=None, rect_size=None, out_dtype=None, fused=True):
     """x: (B, C, H, W) device tensor -> (B, O, h2, w2).
 
     Same result as ops.hex_to_rect(conv(ops.rect_to_hex(x, hex_size)), rect_size)
     with fp32 intermediates (not rounded to out_dtype between stages).
+
+    With fused=True and a `fusable` conv the fused kernel runs under autograd too, wherever
+    its fused backward covers the call (same-size lattices, padding 1 with value 0, a 4-D
+    16/32-bit float x): the gradients of x, conv.kernel and conv.bias then come from
+    hg_pipeline_r2h_conv_h2r_backward and no hex-sized tensor is saved.  The forward values
+    under autograd are therefore the fused kernel's, not the operator chain's; both are within
+    the documented 1e-5 of the oracle.  Elsewhere, and with fused=False, autograd runs through
+    the three operators.
     """
     if out_dtype is None:
         out_dtype = x.dtype if x.dtype in (torch.bfloat16, torch.float16) else torch.float32
-    if fused and fusable(conv) and not torch.is_grad_enabled():
-        y = ops.pipeline_r2h_conv_h2r(x, conv.kernel, conv.bias, hex_size, rect_size,
-                                      conv.pad, conv.groups, int(conv.even_odd_offset),
-                                      float(conv.padding_value), out_dtype)
-        if y is not None:
-            return y
+    if fused and fusable(conv):
+        geom = (hex_size, rect_size, conv.pad, conv.groups, int(conv.even_odd_offset),
+                float(conv.padding_value))
+        if not torch.is_grad_enabled():
+            y = ops.pipeline_r2h_conv_h2r(x, conv.kernel, conv.bias, *geom, out_dtype)
+            if y is not None:
+                return y
+        elif (x.is_cuda and _FORWARD_PAIR(x.dtype, out_dtype)
+              and ops.pipeline_r2h_conv_h2r_backward_workspace(x, out_dtype, conv.kernel,
+                                                               *geom) is not None):
+            return _FusedChainFn.apply(x, conv.kernel, conv.bias, geom, out_dtype)
     h = ops.rect_to_hex(x, hex_size, out_dtype=torch.float32)
     c = conv(h)
     return ops.hex_to_rect(c, rect_size, out_dtype=out_dtype)

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lattice.h"
+
 namespace hg {
 
 // Runs the fused pass if the call is in the kernel's domain (same-size round trip,
@@ -24,5 +26,13 @@ int fused_rt_try(const void* x, void* y, int x_dtype, int y_dtype, int64_t plane
 int fused_conv_try(const void* x, const float* kernel, const float* bias, void* y, int x_dtype,
                    int y_dtype, int64_t batch, int C, int O, int G, int64_t h, int64_t w,
                    int padding, int off, double pad_value, bool epilogue, hipStream_t st);
+
+// Does the same-size streaming kernel cover this r2h lattice (in(r) - r and jn(q) - q in
+// {-1, 0} wherever a tap is inside the raster)?  Exact, O(h1 + w1) fp64 on the host.
+bool fused_geometry_ok(const Geom& g);
+
+// pipeline_bwd.hip: tile rows / columns of the chain's backward passes and the tiles a
+// weight-pass workgroup walks top to bottom (hg_fused_layout md 9).
+void chain_bwd_layout(int* tile_rows, int* tile_cols, int* band_tiles);
 
 }  // namespace hg

@@ -66,7 +66,7 @@ static int fused_channels(const void* x, const float* k, const float* b, void* y
 
 // Does the same-size streaming kernel cover this call?  All checks are exact on the
 // lattice the kernel would compute (O(h1 + w1) fp64 on the host).
-static bool fused_geometry_ok(const Geom& g) {
+bool fused_geometry_ok(const Geom& g) {
     for (int64_t q = 0; q < g.w1; ++q) {            // r2h columns: jn - q in {-1, 0}
         const double j_ = axis_at(g.ys, q) + (double)(g.w - 1) * 0.5;
         const int64_t jn = (int64_t)j_;
@@ -184,12 +184,16 @@ void fused4_layout(int* band_rows, int* win_own, int* win_halo);
 }
 
 // md 0-2: the two-column kernel's modes; md 6: MD 0's four-column variant (fused4.hip: bf16,
-// C = O = 3, widths a multiple of 4).  (md 7 / 8, round 5's four-column round trip and conv,
-// were removed in round 6: HG_EINVAL.)
+// C = O = 3, widths a multiple of 4); md 9: pipeline_bwd.hip's tiles.  (md 7 / 8, round 5's
+// four-column round trip and conv, were removed in round 6: HG_EINVAL.)
 extern "C" int hg_fused_layout(int md, int* band_rows, int* win_own, int* win_halo) {
     if (!band_rows || !win_own || !win_halo) return HG_EINVAL;
     if (md == 6) {
         hg::fused4_layout(band_rows, win_own, win_halo);
+        return HG_OK;
+    }
+    if (md == 9) {   // the chain's backward passes: tile rows, tile columns, tiles per band
+        hg::chain_bwd_layout(band_rows, win_own, win_halo);
         return HG_OK;
     }
     if (md < 0 || md > 2) return HG_EINVAL;

@@ -72,8 +72,10 @@ const char* hg_build_digest(void);
 /* Work decomposition of the streaming fused kernel for mode md (0: hg_pipeline_r2h_conv_h2r,
  * 1: its HexConv2d mode, 2: hg_pipeline_r2h_h2r; 6: mode 0's four-column variant that runs
  * bf16 C = O = 3 calls with widths a multiple of 4): output rows per band, owned columns per
- * window and the window's left halo; HG_EINVAL for any other md.  Host-only; for tests that
- * place inputs at band / window edges. */
+ * window and the window's left halo; md 9: the tiles of hg_pipeline_r2h_conv_h2r_backward
+ * (tile rows, tile columns, and in win_halo the tiles one weight-pass workgroup walks top to
+ * bottom); HG_EINVAL for any other md.  Host-only; for tests that place inputs at band /
+ * window edges. */
 int hg_fused_layout(int md, int* band_rows, int* win_own, int* win_halo);
 
 /* rect -> hex lattice resample.
@@ -247,6 +249,34 @@ int hg_pipeline_r2h_conv_h2r(const void* x, const float* kernel, const float* bi
                              int64_t out_channels, int64_t h, int64_t w, int64_t h1, int64_t w1,
                              int64_t h2, int64_t w2, int padding, int groups,
                              int even_odd_offset, double pad_value, void* stream);
+
+/* Bytes of workspace hg_pipeline_r2h_conv_h2r_backward needs for this call (a positive
+ * multiple of 16), or a negative HG_E* status: HG_EUNSUP outside the backward's domain, which
+ * is the same-size lattice of the forward's streaming kernel: h2 == h1, w2 == w1, a
+ * near-identity rect -> hex lattice (geometry_np.py:440-441), padding 1 with pad value 0,
+ * channels / out_channels / groups in {3/3/1, 3/3/3, 1/1/1}, x_dtype and gy_dtype in {F16,
+ * BF16, F32}, planes below the 32-bit offset limits; widths of either parity.  Launches
+ * nothing; callable without a device. */
+int64_t hg_pipeline_r2h_conv_h2r_backward_workspace(int x_dtype, int gy_dtype, int64_t batch,
+        int64_t channels, int64_t out_channels, int64_t h, int64_t w, int64_t h1, int64_t w1,
+        int64_t h2, int64_t w2, int padding, int groups, int even_odd_offset, double pad_value);
+
+/* Gradients of hg_pipeline_r2h_conv_h2r, i.e. what torch autograd gives the reference chain
+ * rect_to_hex_resample (geometry_np.py:358-519) -> HexConv2d (HexFrames.py:96-169) ->
+ * hex_to_rect_resample (geometry_np.py:191-356), with no hex-sized tensor in memory: the hex
+ * image is recomputed from x on chip.  x: (B, C, h, w) of x_dtype; kernel: (O, C/groups, 7)
+ * float32; gy: (B, O, h2, w2) of gy_dtype.  dx: (B, C, h, w) in x_dtype, dkernel:
+ * (O, C/groups, 7) float32, dbias: (O) float32; any of the three may be NULL (not computed; dx
+ * NULL launches no input pass).  workspace: workspace_bytes >= the query above (used only for
+ * dkernel / dbias).  dkernel and dbias are bit-reproducible from call to call (fixed-order
+ * sums, no atomics); every dx element is written exactly once.  Argument errors (a NULL x, gy
+ * or kernel, a workspace that is too small) are negative statuses reported before any launch;
+ * HG_EUNSUP outside the domain (then differentiate the three operators instead). */
+int hg_pipeline_r2h_conv_h2r_backward(const void* x, const float* kernel, const void* gy,
+        void* dx, float* dkernel, float* dbias, int x_dtype, int gy_dtype, int64_t batch,
+        int64_t channels, int64_t out_channels, int64_t h, int64_t w, int64_t h1, int64_t w1,
+        int64_t h2, int64_t w2, int padding, int groups, int even_odd_offset, double pad_value,
+        void* workspace, int64_t workspace_bytes, void* stream);
 
 /* rect -> hex -> rect round trip (BASELINE config 2) in one pass, no conv: replaces
  * hex_to_rect_resample(rect_to_hex_resample(x, (h1, w1), 'bilinear'), (h1, w1), 'linear')
