@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import fused_variants as FV
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -48,13 +49,9 @@ def _oracle(x, conv):
 
 
 def _up_rows(H):
-    """Rows of the bands k_fused4 walks upwards: odd bands of the full band length."""
-    rows = _abi.fused_layout(6)[0]
-    up = torch.zeros(H, dtype=torch.bool)
-    for k in range(1, H // rows, 2):
-        if (k + 1) * rows <= H:
-            up[k * rows:(k + 1) * rows] = True
-    return up
+    """Rows of the bands k_fused4 walks upwards: odd bands of the full band length (the rule
+    is restated once, in tests/fused_variants.py)."""
+    return torch.from_numpy(FV.up_rows(6, H))
 
 
 def _same(a, b, mask=None):
@@ -65,16 +62,29 @@ def _same(a, b, mask=None):
     up = _up_rows(H).to(a.device)[:, None].expand(H, W)
     sel = torch.ones((H, W), dtype=torch.bool, device=a.device) if mask is None else mask
     fwd, rev = (sel & ~up).expand_as(a), (sel & up).expand_as(a)
-    nbad = int((a.view(torch.int16) != b.view(torch.int16))[fwd].sum().item())
-    assert nbad == 0, f"{nbad} outputs of downward bands differ from the two-column kernel"
+    diff = (a.view(torch.int16) != b.view(torch.int16)) & fwd
+    nbad = int(diff.sum().item())
+    assert nbad == 0, (f"{nbad} outputs of downward bands differ from the two-column kernel: "
+                       + _where(diff))
     if bool(rev.any()):
         fa, fb = a[rev].float(), b[rev].float()
-        assert torch.equal(torch.isnan(fa), torch.isnan(fb))
+        assert torch.equal(torch.isnan(fa), torch.isnan(fb)), \
+            _where(rev & (torch.isnan(a) != torch.isnan(b)))
         fin = torch.isfinite(fb)
-        assert torch.equal(fa[~fin & ~torch.isnan(fb)], fb[~fin & ~torch.isnan(fb)])
+        assert torch.equal(fa[~fin & ~torch.isnan(fb)], fb[~fin & ~torch.isnan(fb)]), \
+            _where(rev & torch.isinf(b) & (a != b))
         d = (fa[fin] - fb[fin]).abs()
         tol = 2.0 ** -7 * torch.maximum(fa[fin].abs(), fb[fin].abs()) + 1e-6
-        assert bool((d <= tol).all()), f"{int((d > tol).sum())} outputs of upward bands beyond one bf16 step"
+        if not bool((d <= tol).all()):
+            af, bf = a.float(), b.float()
+            over = rev & torch.isfinite(bf) & ~((af - bf).abs() <= 2.0 ** -7 * torch.maximum(af.abs(), bf.abs()) + 1e-6)
+            raise AssertionError(f"{int((d > tol).sum())} outputs of upward bands beyond one bf16 step: "
+                                 + _where(over))
+
+
+def _where(bad):
+    """The first bad output and the loop variant that made it (tests/fused_variants.py)."""
+    return FV.describe_first_bad(6, bad.cpu().numpy())
 
 
 def test_layout():
@@ -82,8 +92,11 @@ def test_layout():
     assert rows % 6 == 0 and own == 240 and halo == 8
 
 
-# (B, H, W): one window / band, band and window edges, several of each, the full 4K width
-SHAPES = [(1, 8, 12), (2, 48, 96), (1, 91, 248), (2, 100, 500), (1, 130, 964), (1, 44, 3840)]
+# (B, H, W): one window / band, band and window edges, several of each, the full 4K width;
+# then the shapes whose last band ends on steps 5 and 3 of a block and whose bands and windows
+# run every (cd, rc) loop downwards and upwards (tests/fused_variants.py, pinned by
+# tests/test_fused_variants_cpu.py)
+SHAPES = FV.fused4_shapes()
 
 
 @pytest.mark.parametrize("off", [0, 1])
@@ -107,7 +120,8 @@ def test_fused4_bit_identical_to_two_column_and_vs_oracle(shape, off, monkeypatc
     got = y4[B - 1].double().cpu().numpy()
     tol = 2.0 ** -8 * np.abs(ref) + 1e-5 * np.abs(ref).max()
     bad = np.abs(got - ref) > tol
-    assert not bad.any(), f"{int(bad.sum())} outputs beyond one bf16 rounding of the oracle"
+    assert not bad.any(), (f"{int(bad.sum())} outputs beyond one bf16 rounding of the oracle: "
+                           + FV.describe_first_bad(6, bad))
 
 
 @pytest.mark.parametrize("off", [0, 1])
@@ -115,8 +129,18 @@ def test_fused4_nonfinite_at_band_and_window_edges(off, monkeypatch):
     """Inf / NaN on the four-column kernel's band edges (last row of a band, first of the
     next) and window edges (last owned column of a window, first of the next), the raster's
     corners and edges."""
+    _nonfinite_at_edges(14, off, monkeypatch)
+
+
+@pytest.mark.parametrize("off", [0, 1])
+def test_fused4_nonfinite_at_edges_odd_tail(off, monkeypatch):
+    """The same on an odd height whose last band ends on step 3 of a block (2 rows + 15)."""
+    _nonfinite_at_edges(15, off, monkeypatch)
+
+
+def _nonfinite_at_edges(extra, off, monkeypatch):
     rows, own, _ = _abi.fused_layout(6)
-    H, W = 2 * rows + 14, 2 * own + 16
+    H, W = 2 * rows + extra, 2 * own + 16
     torch.manual_seed(5)
     conv = HexConv2d(3, 3, off, 2, padding=1, bias=True).to(DEV)
     g = torch.Generator(device=DEV).manual_seed(17)

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+import fused_variants as FV
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -21,7 +22,7 @@ pytestmark = pytest.mark.gpu
 if not torch.cuda.is_available():  # pragma: no cover - collected only with -m gpu
     pytest.skip("needs a HIP device", allow_module_level=True)
 
-from HyGrid import ops  # noqa: E402
+from HyGrid import _abi, ops  # noqa: E402
 
 DEV = torch.device("cuda:0")
 
@@ -47,10 +48,11 @@ def _weights(O_, cg, seed):
     return k, b
 
 
-# (B, C, O, groups, h, w): ragged widths vs the 120-column window, odd heights, band
-# edges (126-row bands), tiny rasters
-CASES = [(2, 3, 3, 1, 7, 8), (1, 3, 3, 1, 9, 10), (2, 3, 3, 1, 127, 242), (1, 3, 3, 3, 130, 250),
-         (3, 1, 1, 1, 33, 122), (1, 3, 3, 1, 253, 360), (1, 1, 1, 1, 1, 2), (1, 3, 3, 3, 2, 4)]
+# (B, C, O, groups, h, w): ragged widths vs the window's owned columns, odd heights, tiny
+# rasters, heights next to a multiple of the band length; then shapes built from
+# hg_fused_layout(1) that run a 5-step tail and, for 1/1/1, the inner loop downwards and
+# upwards (tests/fused_variants.py, pinned by tests/test_fused_variants_cpu.py)
+CASES = FV.fconv_cases()
 
 
 @pytest.mark.parametrize("case", CASES)
@@ -69,7 +71,8 @@ def test_fused_conv_fp32_vs_oracle(case, off, bias):
                       None if b is None else b.cpu().double().numpy(), off, 2, padding=1,
                       groups=G)
     scale = max(np.abs(ref).max(), 1e-30)
-    np.testing.assert_allclose(y, ref, rtol=1e-5, atol=1e-5 * scale)
+    msg = FV.describe_first_bad(1, ~(np.abs(y - ref) <= 1e-5 * scale + 1e-5 * np.abs(ref)))
+    np.testing.assert_allclose(y, ref, rtol=1e-5, atol=1e-5 * scale, err_msg=msg)
 
 
 @pytest.mark.parametrize("dt_in,dt_out", [(torch.bfloat16, torch.bfloat16),
@@ -103,8 +106,9 @@ def test_fused_conv_4k_batch_matches_stream_kernel():
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("off", [0, 1])
 def test_fused_conv_nan_inf_positions_match_stream_kernel(dt, off):
-    """Non-finite inputs on the raster border, at the 120-column window edges and at the
-    126-row band edges: MD 1 builds its padding by selecting zeros (fused_kernel.h), so a
+    """Non-finite inputs on the raster border, at the window edges and at the band edges
+    (from hg_fused_layout(1), and at rows 125 .. 252 where round 1's 126-row bands ended):
+    MD 1 builds its padding by selecting zeros (fused_kernel.h), so a
     boundary row's or column's NaN must reach exactly the outputs whose taps read it,
     as in the register-streaming kernel (HYGRID_FCONV=0)."""
     B, C, h, w = 2, 3, 260, 372
@@ -118,8 +122,11 @@ def test_fused_conv_nan_inf_positions_match_stream_kernel(dt, off):
     x[1, 0, 77, w - 1] = nan              # last column
     for c0 in (119, 120, 239, 240, 359, 360):   # window edges (owned columns 0..119, ...)
         x[1, 1, 30 + c0 % 7, c0] = nan
-    for r0 in (125, 126, 251, 252):       # band edges (126-row bands)
+    for r0 in (125, 126, 251, 252):       # (band edges of the first 126-row bands)
         x[1, 2, r0, 61 + r0 % 5] = inf
+    rows, own, _ = _abi.fused_layout(1)
+    for r0 in (rows - 1, rows, 2 * rows - 1, 2 * rows):     # band edges, down -> up -> down
+        x[1, 2, r0, own + 3 + r0 % 5] = inf
     x = x.to(dt)
     y = ops.hexconv2d(x, k, b, off, 2, padding=1, out_dtype=torch.float32)
     ref = _other_kernel(ops.hexconv2d, x, k, b, off, 2, padding=1, out_dtype=torch.float32)
@@ -136,7 +143,6 @@ def test_fused_conv_nan_inf_positions_match_stream_kernel(dt, off):
 
 
 def test_removed_layout_modes_are_invalid():
-    from HyGrid import _abi
     for md in (7, 8):
         with pytest.raises(ValueError):
             _abi.fused_layout(md)

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import fused_variants as FV
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -20,10 +21,15 @@ from HyGrid.pipeline import rect_hex_conv_rect  # noqa: E402
 DEV = torch.device("cuda:0")
 
 
-def close(y, ref, rtol):
+def close(y, ref, rtol, md=None):
+    """md: the streaming kernel mode that made y; a failure then names the first bad element
+    and the loop variant of its wave (tests/fused_variants.py)."""
     y = np.asarray(y, np.float64)
     scale = max(np.abs(ref).max(), 1e-30)
-    np.testing.assert_allclose(y, ref, rtol=rtol, atol=rtol * scale)
+    msg = ""
+    if md is not None:
+        msg = FV.describe_first_bad(md, ~(np.abs(y - ref) <= rtol * scale + rtol * np.abs(ref)))
+    np.testing.assert_allclose(y, ref, rtol=rtol, atol=rtol * scale, err_msg=msg)
 
 
 def one_rounding(got, ref, ulp=2.0 ** -8):
@@ -64,6 +70,10 @@ CASES = [
     (1, 3, 6, 4, None, None, 0, 1, 1, 0.0),         # smaller than one window / band
     (1, 3, 127, 122, None, None, 1, 1, 3, 0.0),     # band and window edges
 ]
+# k_fused MD 0's loop variants: every (cd, rc) class for each channel configuration and offset,
+# every tail and block bucket for each offset (tests/fused_variants.py, pinned by
+# tests/test_fused_variants_cpu.py)
+CASES += [(B, C, H, W, None, None, off, 1, g, 0.0) for B, C, H, W, off, g in FV.md0_cases()]
 
 
 @pytest.mark.parametrize("case", CASES)
@@ -79,7 +89,8 @@ def test_fused_vs_oracle_fp32(case):
     hs_ = hs or (H, W)
     ho, wo = ops.hexconv2d_out_shape(hs_[0], hs_[1], 2, 1, pad, 1)
     ref = oracle_chain(x, conv, hs_, rs or (ho, wo))
-    close(y.cpu().numpy(), ref, 1e-5)
+    streamed = hs is None and rs is None and pad == 1 and pv == 0.0 and W % 2 == 0
+    close(y.cpu().numpy(), ref, 1e-5, 0 if streamed else None)
 
 
 def test_fused_4k_bf16_matches_oracle_and_unfused():

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import fused_variants as FV
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -28,8 +29,9 @@ def oracle_roundtrip(x):
     return O.hex_to_rect(hx, (H, W), 1).reshape(xd.shape)
 
 
-@pytest.mark.parametrize("shape", [(2, 3, 64, 130), (1, 1, 37, 250), (3, 2, 200, 96),
-                                   (1, 3, 131, 246), (1, 1, 2, 4), (2, 3, 135, 968)])
+# the list lives in tests/fused_variants.py: tests/test_fused_variants_cpu.py pins that it
+# reaches every loop variant of k_fused MD 2
+@pytest.mark.parametrize("shape", FV.roundtrip_shapes())
 def test_roundtrip_fp32_vs_oracle(shape):
     g = torch.Generator().manual_seed(sum(shape))
     x = torch.rand(shape, generator=g).to(DEV)
@@ -37,7 +39,9 @@ def test_roundtrip_fp32_vs_oracle(shape):
     assert y is not None and y.shape == x.shape and y.dtype == torch.float32
     ref = oracle_roundtrip(x)
     scale = np.abs(ref).max()
-    np.testing.assert_allclose(y.double().cpu().numpy(), ref, rtol=1e-5, atol=1e-5 * scale)
+    got = y.double().cpu().numpy()
+    msg = FV.describe_first_bad(2, ~(np.abs(got - ref) <= 1e-5 * scale + 1e-5 * np.abs(ref)))
+    np.testing.assert_allclose(got, ref, rtol=1e-5, atol=1e-5 * scale, err_msg=msg)
 
 
 def test_roundtrip_1080p_fp32_full_image_vs_oracle():
