@@ -56,6 +56,8 @@ SIGNATURES = {
     "hg_resample_kernel": ([_int, _int, _int] + [_i64] * 5 + [_int], _int),
     "hg_hexconv2d_out_shape": ([_i64, _i64, _int, _int, _int, _int,
                                 ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _int),
+    "hg_hexconv2d_generic_plan": ([_int] + [_i64] * 5 + [_int] * 6 + [ctypes.POINTER(_int)] * 4
+                                  + [ctypes.POINTER(_i64)], _int),
     "hg_hexconv2d": ([_vp, _vp, _vp, _vp, _int, _int, _int, _i64, _i64, _i64, _i64, _i64,
                       _int, _int, _int, _int, _int, _int, _int, _dbl, _vp], _int),
     "hg_hexconv2d_epilogue": ([_vp, _vp, _vp, _vp, _int, _int, _int, _i64, _i64, _i64, _i64,
@@ -149,6 +151,21 @@ def pyramid_level_kernel(x_dtype, y_dtype, batch, channels, h, w, h1, w1, even_o
     if st < 0:
         check(st, "hg_hex_pyramid_level_kernel")
     return st
+
+
+def hexconv2d_generic_plan(w_dtype, batch, in_channels, out_channels, h, w, radius, stride=1,
+                           padding=0, dilation=1, groups=1, even_odd_offset=0):
+    """dict(direct, cib, ocb, bc, tiles): what hg_hexconv2d's generic kernels (k_hexconv, or
+    k_hexconv_direct when direct) would be launched with for this layer; nothing is launched.
+    Not whether the streaming or the MFMA kernel takes the call first."""
+    direct, cib, ocb, bc, tiles = _int(), _int(), _int(), _int(), _i64()
+    check(lib().hg_hexconv2d_generic_plan(
+        int(w_dtype), int(batch), int(in_channels), int(out_channels), int(h), int(w),
+        int(radius), int(stride), int(padding), int(dilation), int(groups), int(even_odd_offset),
+        ctypes.byref(direct), ctypes.byref(cib), ctypes.byref(ocb), ctypes.byref(bc),
+        ctypes.byref(tiles)), "hg_hexconv2d_generic_plan")
+    return dict(direct=bool(direct.value), cib=cib.value, ocb=ocb.value, bc=bc.value,
+                tiles=tiles.value)
 
 
 def strerror(status):

@@ -195,16 +195,64 @@ __global__ __launch_bounds__(256) void k_hexconv_direct(const Tin* __restrict__ 
     y[idx] = from_acc<Tout>(acc);
 }
 
-template <typename Tin, typename Tout, typename A, int OCB, int KFIX>
-static int launch_conv(const void* x, const void* k, const void* b, void* y, ConvGeom G,
-                       hipStream_t st) {
-    const int64_t nty = (G.ho + CV_TR - 1) / CV_TR;
-    const int64_t tiles = (int64_t)G.ntx * nty;
-    int64_t nchunk = std::max<int64_t>(1, std::min<int64_t>((2048 + tiles - 1) / tiles, G.B));
+// Launch plan of the generic kernels: everything the host decides before k_hexconv /
+// k_hexconv_direct start.  Stated once here; hg_hexconv2d_epilogue launches from it and
+// hg_hexconv2d_generic_plan reports it (nothing is launched there).
+struct ConvPlan {
+    int direct;       // 1: k_hexconv_direct (one channel's footprint exceeds the LDS budget)
+    int cib;          // input channels staged per pass (0 when direct)
+    int ocb;          // output channels per accumulation pass, the OCB template argument
+    int bc;           // images per workgroup
+    int ntx;          // tiles along output columns
+    int nPr, pitch;   // LDS footprint rows / pitch (elements) of one channel
+    int mink;         // min column tap offset over both parities
+    int64_t tiles;    // grid.x: output tiles (k_hexconv) or 256-sample blocks (direct)
+};
+
+static ConvPlan conv_plan(int w_dtype, int64_t B, int64_t O, int cg, int og, int64_t ho,
+                          int64_t wo, int r, int s, int p, int d, int off) {
+    ConvPlan P = {};
+    const int K = 3 * r * r - 3 * r + 1;
+    P.ntx = (int)((wo + CV_TC - 1) / CV_TC);
+    // column span of the taps over both row parities
+    const int op = (off + p) & 1;
+    int mink = INT_MAX, maxk = INT_MIN, maxdy = 0;
+    for (int t = 0; t < K; ++t) {
+        int dy, d0, d1;
+        tap_geom(r, s, d, op, t, &dy, &d0, &d1);
+        mink = std::min(mink, std::min(d0, d1));
+        maxk = std::max(maxk, std::max(d0, d1));
+        maxdy = std::max(maxdy, dy);
+    }
+    P.mink = mink;
+    P.nPr = s * (CV_TR - 1) + maxdy + 1;
+    P.pitch = s * (CV_TC - 1) + (maxk - mink) + 1;
+    P.pitch = (P.pitch + 3) & ~3;
+    P.bc = 1;
+    const size_t esz = w_dtype == HG_F64 ? 8 : 4;
+    const size_t per = (size_t)P.nPr * P.pitch * esz;
+    if (per + 3 * CV_MAXK * sizeof(int) > (size_t)CV_LDS_BUDGET) {
+        P.direct = 1;   // footprint too large for LDS: direct-gather kernel
+        P.ocb = 1;
+        P.tiles = (B * O * ho * wo + 255) / 256;
+        return P;
+    }
+    P.cib = (int)std::min<size_t>((size_t)cg, (CV_LDS_BUDGET - 3 * CV_MAXK * sizeof(int)) / per);
+    P.ocb = (og % 4 == 0 || og > 4) ? 4 : og;   // og 1 / 2 / 3 have kernels of their own
+    const int64_t nty = (ho + CV_TR - 1) / CV_TR;
+    P.tiles = (int64_t)P.ntx * nty;
+    // a workgroup takes several images once the grid has ~2048 workgroups without them
+    int64_t nchunk = std::max<int64_t>(1, std::min<int64_t>((2048 + P.tiles - 1) / P.tiles, B));
     nchunk = std::min<int64_t>(nchunk, 65535);
-    G.bc = (int)((G.B + nchunk - 1) / nchunk);
+    P.bc = (int)((B + nchunk - 1) / nchunk);
+    return P;
+}
+
+template <typename Tin, typename Tout, typename A, int OCB, int KFIX>
+static int launch_conv(const void* x, const void* k, const void* b, void* y, const ConvGeom& G,
+                       const ConvPlan& P, hipStream_t st) {
     const size_t shmem = 3 * CV_MAXK * sizeof(int) + (size_t)G.cib * G.nPr * G.pitch * sizeof(A);
-    dim3 grid((unsigned)tiles, (unsigned)((G.B + G.bc - 1) / G.bc));
+    dim3 grid((unsigned)P.tiles, (unsigned)((G.B + G.bc - 1) / G.bc));
     hipLaunchKernelGGL((k_hexconv<Tin, Tout, A, OCB, KFIX>), grid, dim3(CV_THREADS), shmem, st,
                        (const Tin*)x, (const A*)k, (const A*)b, (Tout*)y, G);
     return launch_status();
@@ -212,26 +260,27 @@ static int launch_conv(const void* x, const void* k, const void* b, void* y, Con
 
 template <typename Tin, typename Tout, typename A>
 static int conv_dispatch(const void* x, const void* k, const void* b, void* y,
-                         const ConvGeom& G, hipStream_t st) {
-    if (G.cib == 0) {
-        const int64_t total = G.B * G.O * G.ho * G.wo;
-        hipLaunchKernelGGL((k_hexconv_direct<Tin, Tout, A>), dim3((unsigned)((total + 255) / 256)),
+                         const ConvGeom& G, const ConvPlan& P, hipStream_t st) {
+    if (P.direct) {
+        hipLaunchKernelGGL((k_hexconv_direct<Tin, Tout, A>), dim3((unsigned)P.tiles),
                            dim3(256), 0, st, (const Tin*)x, (const A*)k, (const A*)b, (Tout*)y, G);
         return launch_status();
     }
     const bool k7 = G.K == 7;
-    if (G.og % 4 == 0 || G.og > 4) {
-        return k7 ? launch_conv<Tin, Tout, A, 4, 7>(x, k, b, y, G, st)
-                  : launch_conv<Tin, Tout, A, 4, 0>(x, k, b, y, G, st);
+    switch (P.ocb) {
+    case 4:
+        return k7 ? launch_conv<Tin, Tout, A, 4, 7>(x, k, b, y, G, P, st)
+                  : launch_conv<Tin, Tout, A, 4, 0>(x, k, b, y, G, P, st);
+    case 3:
+        return k7 ? launch_conv<Tin, Tout, A, 3, 7>(x, k, b, y, G, P, st)
+                  : launch_conv<Tin, Tout, A, 3, 0>(x, k, b, y, G, P, st);
+    case 2:
+        return k7 ? launch_conv<Tin, Tout, A, 2, 7>(x, k, b, y, G, P, st)
+                  : launch_conv<Tin, Tout, A, 2, 0>(x, k, b, y, G, P, st);
+    default:
+        return k7 ? launch_conv<Tin, Tout, A, 1, 7>(x, k, b, y, G, P, st)
+                  : launch_conv<Tin, Tout, A, 1, 0>(x, k, b, y, G, P, st);
     }
-    if (G.og == 3)
-        return k7 ? launch_conv<Tin, Tout, A, 3, 7>(x, k, b, y, G, st)
-                  : launch_conv<Tin, Tout, A, 3, 0>(x, k, b, y, G, st);
-    if (G.og == 2)
-        return k7 ? launch_conv<Tin, Tout, A, 2, 7>(x, k, b, y, G, st)
-                  : launch_conv<Tin, Tout, A, 2, 0>(x, k, b, y, G, st);
-    return k7 ? launch_conv<Tin, Tout, A, 1, 7>(x, k, b, y, G, st)
-              : launch_conv<Tin, Tout, A, 1, 0>(x, k, b, y, G, st);
 }
 
 int launch_conv_stream(const void* x, const float* k, const float* b, void* y, int x_dtype,
@@ -251,6 +300,31 @@ int hg_hexconv2d_out_shape(int64_t h, int64_t w, int radius, int stride, int pad
                            int dilation, int64_t* ho, int64_t* wo) {
     if (!ho || !wo) return HG_EINVAL;
     return hg::conv_out_shape(h, w, radius, stride, padding, dilation, ho, wo);
+}
+
+int hg_hexconv2d_generic_plan(int w_dtype, int64_t batch, int64_t in_channels,
+                              int64_t out_channels, int64_t h, int64_t w, int radius, int stride,
+                              int padding, int dilation, int groups, int even_odd_offset,
+                              int* direct, int* cib, int* ocb, int* bc, int64_t* tiles) {
+    using namespace hg;
+    if (!direct || !cib || !ocb || !bc || !tiles) return HG_EINVAL;
+    int64_t ho, wo;
+    int st = conv_out_shape(h, w, radius, stride, padding, dilation, &ho, &wo);
+    if (st) return st;
+    st = conv_check_args(batch, in_channels, out_channels, h, w, groups, padding,
+                         HG_PAD_CONSTANT);
+    if (st) return st;
+    if (3 * radius * radius - 3 * radius + 1 > CV_MAXK) return HG_EUNSUP;
+    if (w_dtype != HG_F32 && w_dtype != HG_F64) return HG_EDTYPE;
+    if (h * w >= INT_MAX / 2 || ho * wo >= INT_MAX / 2) return HG_ESHAPE;
+    *direct = *cib = *ocb = *bc = 0;
+    *tiles = 0;
+    if (batch == 0 || ho == 0 || wo == 0) return HG_OK;   // nothing would be launched
+    const ConvPlan P = conv_plan(w_dtype, batch, out_channels, (int)(in_channels / groups),
+                                 (int)(out_channels / groups), ho, wo, radius, stride, padding,
+                                 dilation, even_odd_offset & 1);
+    *direct = P.direct; *cib = P.cib; *ocb = P.ocb; *bc = P.bc; *tiles = P.tiles;
+    return HG_OK;
 }
 
 int hg_hexconv2d(const void* x, const void* kernel, const void* bias, void* y, int x_dtype,
@@ -309,36 +383,17 @@ int hg_hexconv2d_epilogue(const void* x, const void* kernel, const void* bias, v
     G.epi = epi;
     G.cg = (int)(in_channels / groups);
     G.og = (int)(out_channels / groups);
-    G.ntx = (int)((G.wo + CV_TC - 1) / CV_TC);
-    // column span of the taps over both row parities
-    const int op = (G.off + G.p) & 1;
-    int mink = INT_MAX, maxk = INT_MIN, maxdy = 0;
-    for (int t = 0; t < G.K; ++t) {
-        int dy, d0, d1;
-        tap_geom(radius, stride, dilation, op, t, &dy, &d0, &d1);
-        mink = std::min(mink, std::min(d0, d1));
-        maxk = std::max(maxk, std::max(d0, d1));
-        maxdy = std::max(maxdy, dy);
-    }
-    G.mink = mink;
-    G.nPr = stride * (CV_TR - 1) + maxdy + 1;
-    G.pitch = stride * (CV_TC - 1) + (maxk - mink) + 1;
-    G.pitch = (G.pitch + 3) & ~3;
-    const size_t esz = w_dtype == HG_F64 ? 8 : 4;
-    const size_t per = (size_t)G.nPr * G.pitch * esz;
-    if (per + 3 * CV_MAXK * sizeof(int) > (size_t)CV_LDS_BUDGET)
-        G.cib = 0;   // footprint too large for LDS: direct-gather kernel
-    else
-        G.cib = (int)std::min<size_t>((size_t)G.cg,
-                                      (CV_LDS_BUDGET - 3 * CV_MAXK * sizeof(int)) / per);
-    G.bc = 1;
+    const ConvPlan P = conv_plan(w_dtype, G.B, G.O, G.cg, G.og, G.ho, G.wo, radius, stride,
+                                 padding, dilation, G.off);
+    G.ntx = P.ntx; G.mink = P.mink; G.nPr = P.nPr; G.pitch = P.pitch;
+    G.cib = P.cib; G.bc = P.bc;
     if (w_dtype == HG_F64) {
         HG_DISPATCH_IN(x_dtype, TIN, HG_DISPATCH_FLOAT_OUT(y_dtype, TOUT, {
-            return conv_dispatch<TIN, TOUT, double>(x, kernel, bias, y, G, s);
+            return conv_dispatch<TIN, TOUT, double>(x, kernel, bias, y, G, P, s);
         }));
     } else {
         HG_DISPATCH_IN(x_dtype, TIN, HG_DISPATCH_FLOAT_OUT(y_dtype, TOUT, {
-            return conv_dispatch<TIN, TOUT, float>(x, kernel, bias, y, G, s);
+            return conv_dispatch<TIN, TOUT, float>(x, kernel, bias, y, G, P, s);
         }));
     }
     return HG_EDTYPE;

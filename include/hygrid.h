@@ -140,6 +140,22 @@ int hg_lattice_maps(int op, int64_t h, int64_t w, int64_t h1, int64_t w1, int32_
 int hg_hexconv2d_out_shape(int64_t h, int64_t w, int radius, int stride, int padding,
                            int dilation, int64_t* ho, int64_t* wo);
 
+/* Launch plan of hg_hexconv2d's generic kernels for this layer (nothing is launched, no device
+ * is touched): what k_hexconv / k_hexconv_direct would be started with if the call reached
+ * them.  Whether the register-streaming or the MFMA kernel takes the call first is not
+ * answered here.  direct: 1 when one channel's tile footprint exceeds the LDS budget
+ * (k_hexconv_direct; then cib = 0, ocb = 1, bc = 1 and tiles = its 256-sample blocks);
+ * cib: input channels per group staged in LDS per pass (<= in_channels / groups; the pass
+ * count is ceil((in_channels / groups) / cib)); ocb: output channels accumulated per pass
+ * (4, or out_channels / groups when that is 1, 2 or 3); bc: images one workgroup walks;
+ * tiles: 16-row x 128-column output tiles per image.  w_dtype: HG_F32 or HG_F64 (the LDS
+ * element).  All outputs 0 for an empty call.  Introspection for tests, which derive the
+ * code path of a shape from it instead of hard-coding it; the reference has no counterpart. */
+int hg_hexconv2d_generic_plan(int w_dtype, int64_t batch, int64_t in_channels,
+                              int64_t out_channels, int64_t h, int64_t w, int radius, int stride,
+                              int padding, int dilation, int groups, int even_odd_offset,
+                              int* direct, int* cib, int* ocb, int* bc, int64_t* tiles);
+
 /* HexConv2d forward.  Replaces HexFrames.HexConv2d.forward (HexFrames.py:96-169)
  * including pad (:13-21) and heximage_to_type1 (:417-445), which are folded into
  * index arithmetic: no type1 image is materialised.

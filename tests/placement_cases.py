@@ -25,6 +25,7 @@ ULP = {BF16: 2.0 ** -8, F16: 2.0 ** -11}
 EXEMPT = {
     "hg_fused_layout": "host-only query; band_rows / win_own / win_halo are host ints",
     "hg_hexconv2d_out_shape": "host-only shape rule; ho / wo are host int64s",
+    "hg_hexconv2d_generic_plan": "host-only query; direct / cib / ocb / bc / tiles are host ints",
 }
 
 

@@ -56,15 +56,16 @@ def test_backward_vs_reference_autograd(golden, golden_index):
 
 
 @pytest.mark.parametrize("mode", ["constant", "reflect", "replicate", "circular"])
-@pytest.mark.parametrize("p", [(2, 1, 1, 1, 3), (3, 2, 2, 2, 1), (2, 1, 1, 3, 3)])
+@pytest.mark.parametrize("p", [(2, 1, 1, 1, 3), (3, 2, 2, 2, 1), (2, 1, 1, 3, 3),
+                               (2, 2, 1, 1, 4, 24, 28)])    # a wide grouped layer: 24 -> 28
 def test_autograd_module_vs_oracle(mode, p):
     """HexConv2d(...).backward through torch autograd on the GPU against the fp64
     adjoint oracle on the same data (x.grad, kernel.grad, bias.grad)."""
-    r, s, d, pad, groups = p
+    r, s, d, pad, groups, C, O_ = p if len(p) == 7 else p + (3, 6)
     torch.manual_seed(7)
-    m = HexConv2d(3, 6, 1, r, stride=s, padding=pad, dilation=d, groups=groups, bias=True,
+    m = HexConv2d(C, O_, 1, r, stride=s, padding=pad, dilation=d, groups=groups, bias=True,
                   padding_mode=mode, padding_value=0.25).to(DEV)
-    x = torch.rand((2, 3, 31, 45), device=DEV, requires_grad=True)
+    x = torch.rand((2, C, 31, 45), device=DEV, requires_grad=True)
     y = m(x)
     gy = torch.randn_like(y)
     y.backward(gy)

@@ -18,9 +18,11 @@ DEV = torch.device("cuda:0")
 
 ACTS = [dict(type="ReLU"), dict(type="LeakyReLU", negative_slope=0.1), dict(type="ReLU6"),
         dict(type="Sigmoid"), dict(type="Tanh"), None]
-SHAPES = [  # (C, O, radius, stride, groups, padding): stream path, LDS path, direct path
+SHAPES = [  # (C, O, radius, stride, groups, padding): stream path (3 -> 3, 1 -> 1), MFMA path
+    # (8 -> 16: O >= 16), LDS path (4 -> 8 radius 3 in one channel pass, 3 -> 6 stride 2 one
+    # channel per pass) and, last, a multi-chunk LDS layer with a ragged last chunk (8 -> 12)
     (3, 3, 2, 1, 1, 1), (3, 3, 2, 1, 3, 1), (8, 16, 2, 1, 1, 1), (4, 8, 3, 1, 2, 2),
-    (3, 6, 2, 2, 1, 1), (1, 1, 2, 1, 1, 0)]
+    (3, 6, 2, 2, 1, 1), (1, 1, 2, 1, 1, 0), (8, 12, 2, 1, 1, 1)]
 
 
 def _randomize_bn(bn, seed):
