@@ -400,6 +400,26 @@ def hexconv2d_backward(gy, x, kernel, bias, cfg, need_x=True, need_k=True, need_
     return dx, gk, gb
 
 
+def hexconv2d_backward_plan(x_dtype, w_dtype, batch, in_channels, out_channels, h, w, radius,
+                            stride=1, padding=0, dilation=1, groups=1, padding_mode="constant"):
+    """(d input kernel, d kernel kernel) of hexconv2d_backward for this layer, each
+    _abi.HG_CONV_BWD_GENERIC or _abi.HG_CONV_BWD_MFMA (hg_hexconv2d_backward_plan): which
+    kernels the call would run, HYGRID_CONV_BWD_MFMA included.  Nothing is launched and no
+    device is needed.  x_dtype / w_dtype: torch dtypes or hg_dtype codes."""
+    pm = _abi.PAD_MODES.get(padding_mode)
+    if pm is None:
+        raise ValueError(f"unsupported padding_mode {padding_mode!r}")
+    xd = x_dtype if isinstance(x_dtype, int) else _abi.dtype_code(x_dtype)
+    wd = w_dtype if isinstance(w_dtype, int) else _abi.dtype_code(w_dtype)
+    dxk, dwk = ctypes.c_int(), ctypes.c_int()
+    st = _abi.lib().hg_hexconv2d_backward_plan(
+        xd, wd, int(batch), int(in_channels), int(out_channels), int(h), int(w), int(radius),
+        int(stride), int(padding), int(dilation), int(groups), pm, ctypes.byref(dxk),
+        ctypes.byref(dwk))
+    _abi.check(st, "hg_hexconv2d_backward_plan")
+    return dxk.value, dwk.value
+
+
 def hex_to_type1(x, even_odd_offset, row_repeat=1, out_dtype=None):
     """Offset-row hex raster (..., H, W) -> type1 (..., H*row_repeat, 2W+1) on the GPU
     (hg_hex_to_type1): row_repeat 1 = HexFrames.heximage_to_type1 (HexFrames.py:417-445),

@@ -24,36 +24,14 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "conv_mfma.h"
 #include "hexconv_geom.h"
 
 namespace hg {
 
-constexpr int CM_THREADS = 256;
-constexpr int CM_ROWS = 4;                  // output rows per workgroup (one per wave)
-constexpr int CM_Q = 64;                    // output columns per workgroup
-constexpr int CM_OMAX = 64;                 // output channels per workgroup (NOT = 4 tiles;
-                                            // 2 tiles = 32 channels when O <= 32)
-constexpr int CM_CC = 8;                    // input channels per LDS chunk (28.6 KB LDS: 4 WGs per CU)
-constexpr int CM_PR = CM_ROWS + 2;          // staged P rows (taps reach rows r .. r+2)
-constexpr int CM_PP = 72;                   // staged P pitch: 64 + tap column span (<= 4),
-                                            // 6*72 = 432 = 16 mod 32 banks: conflict-free B reads
-constexpr int CM_CST = CM_PR * CM_PP;       // P channel stride
-constexpr int CM_WST = 7 * CM_OMAX + 16;    // weight channel stride (= 16 mod 32 banks)
-
-typedef float cm_f4 __attribute__((ext_vector_type(4)));
 #ifndef CM_TD
 #define CM_TD 1                             // MFMA kernels, 16-bit outputs: D as [column][channel] (below)
 #endif
-
-struct MfmaGeom {
-    int64_t B;
-    int C, O, h, w, ho, wo, p, pad_mode;
-    int mink;                   // smallest tap column offset over both parities
-    int dy[7], dk[2][7];        // tap rows / columns (padded frame, relative to mink)
-    int ntq, ntr, nto;          // tiles along columns / rows / output channels
-    float pad_value;
-    Epilogue epi;
-};
 
 // CM_TD epilogue (16-bit outputs): lane (li, lk) holds output channel oc + 16 ot, columns
 // q + 16 qt .. + 3 in its 4 registers: one 8-B store per (ot, qt) when every row's start keeps
@@ -107,7 +85,6 @@ __global__ __launch_bounds__(CM_THREADS) void k_hexconv_mfma(const Tin* __restri
     const int q0 = tq * CM_Q, r0 = tr * CM_ROWS, o0 = to * (16 * NOT);
     const int r = r0 + wv;                               // this wave's output row
     const int par = r & 1;
-    const int Wp = G.w + 2 * G.p, Hp = G.h + 2 * G.p;
     const int li = lane & 15, lk = lane >> 4;            // fragment row / k of this lane
 
     // 16-bit outputs only (fp32 outputs as two 8-B stores: 3.9 % slower than 2-B stores,
@@ -128,28 +105,7 @@ __global__ __launch_bounds__(CM_THREADS) void k_hexconv_mfma(const Tin* __restri
     const Tin* xb = x + b * (int64_t)G.C * G.h * G.w;
     for (int c0 = 0; c0 < G.C; c0 += CM_CC) {
         // ---- stage P rows r0 .. r0+5 (padded frame), columns q0 + mink + (0..71) ---------
-        // 216 threads = 72 columns x 3 row phases; each thread keeps its column's source
-        // index (padding rules applied once) and walks rows pr = phase, phase + 3, ... of
-        // every channel of the chunk.  (Loading the next chunk into registers during the
-        // MFMAs instead needs ~60 more VGPRs and spilled at 2 waves per SIMD.)
-        if (tid < 3 * CM_PP) {
-            const int pc = tid % CM_PP, ph = tid / CM_PP;
-            const int px = q0 + G.mink + pc;
-            const bool zc = px >= Wp;                        // type1 structural zero column
-            const int64_t xi = zc ? -1 : pad_map(px - G.p, G.w, G.pad_mode);
-#pragma unroll 4
-            for (int rr = ph; rr < CM_CC * CM_PR; rr += 3) {
-                const int cc = rr / CM_PR, pr = rr - cc * CM_PR;
-                const int c = c0 + cc, py = r0 + pr;
-                float v = 0.f;
-                if (!zc && c < G.C && py < Hp) {
-                    const int64_t yi = pad_map(py - G.p, G.h, G.pad_mode);
-                    v = (yi < 0 || xi < 0) ? G.pad_value
-                                           : (float)xb[((int64_t)c * G.h + yi) * G.w + xi];
-                }
-                ps[cc * CM_CST + pr * CM_PP + pc] = v;
-            }
-        }
+        cm_stage_p(ps, xb, G, c0, q0, r0, tid);
         // ---- stage weights W[o0 .. o0+63][c0 .. c0+CM_CC-1][t] as [c][t][o] --------------
         // per output channel the chunk's CM_CC x 7 = 56 weights are contiguous: 14 float4 loads
         for (int e = tid; e < CM_O * (CM_CC * 7 / 4); e += CM_THREADS) {
@@ -680,31 +636,10 @@ int conv_mfma_try(const void* x, const float* k, const float* b, void* y, int x_
     if (env_is("HYGRID_CONV_MFMA", "0")) return HG_EUNSUP;   // A/B switch: generic kernels
     if (radius != 2 || stride != 1 || dilation != 1 || groups != 1) return HG_EUNSUP;
     if (C < 1 || O < 16 || padding < 0 || padding > 2) return HG_EUNSUP;
-    if (C > INT_MAX / 16 || O > INT_MAX / 16 || h > INT_MAX / 4 || w > INT_MAX / 4) return HG_EUNSUP;
-    if (C * h * w * 4 >= ((int64_t)1 << 31)) return HG_EUNSUP;   // 32-bit buffer offsets
+    if (!conv_mfma_size_ok(C, O, h, w)) return HG_EUNSUP;       // 32-bit buffer offsets
     MfmaGeom G = {};
-    G.B = B; G.C = (int)C; G.O = (int)O; G.h = (int)h; G.w = (int)w; G.p = padding;
-    G.pad_mode = pad_mode; G.pad_value = (float)pad_value; G.epi = epi;
-    int64_t ho, wo;
-    if (conv_out_shape(h, w, radius, stride, padding, dilation, &ho, &wo)) return HG_EUNSUP;
-    G.ho = (int)ho; G.wo = (int)wo;
-    const int op = (off + padding) & 1;
-    int mink = INT_MAX, maxk = INT_MIN;
-    int dyv[7], dk0[7], dk1[7];
-    for (int t = 0; t < 7; ++t) {
-        tap_geom(radius, stride, dilation, op, t, &dyv[t], &dk0[t], &dk1[t]);
-        mink = std::min(mink, std::min(dk0[t], dk1[t]));
-        maxk = std::max(maxk, std::max(dk0[t], dk1[t]));
-    }
-    if (maxk - mink + CM_Q > CM_PP) return HG_EUNSUP;
-    G.mink = mink;
-    for (int t = 0; t < 7; ++t) {
-        G.dy[t] = dyv[t];
-        G.dk[0][t] = dk0[t] - mink;
-        G.dk[1][t] = dk1[t] - mink;
-    }
-    G.ntq = (G.wo + CM_Q - 1) / CM_Q;
-    G.ntr = (G.ho + CM_ROWS - 1) / CM_ROWS;
+    if (!conv_mfma_forward_geom(G, B, C, O, h, w, padding, off, pad_mode, pad_value)) return HG_EUNSUP;
+    G.epi = epi;
     // output-channel tiles per workgroup (A/B switch HYGRID_CONV_NT=2: two for any O)
     const int nt = (G.O <= 32 || env_is("HYGRID_CONV_NT", "2")) ? 2 : 4;
     G.nto = (G.O + 16 * nt - 1) / (16 * nt);
@@ -749,6 +684,14 @@ int conv_mfma_try(const void* x, const float* k, const float* b, void* y, int x_
         HG_CB_LAUNCH(float)
 #undef HG_CB_LAUNCH
     }
+    return conv_mfma_launch_f32(x, k, b, y, x_dtype, y_dtype, G, nt, st);
+}
+
+int conv_mfma_launch_f32(const void* x, const float* k, const float* b, void* y, int x_dtype,
+                         int y_dtype, const MfmaGeom& G, int nt, hipStream_t st) {
+    const int64_t blocks = G.B * (int64_t)G.ntq * G.ntr * G.nto;
+    if (blocks > INT_MAX || blocks <= 0) return blocks == 0 ? HG_OK : HG_EUNSUP;
+    const dim3 grid((unsigned)blocks), blk(CM_THREADS);
 #define HG_CM_LAUNCH(TI, TO)                                                                  \
     if (nt == 2)                                                                              \
         hipLaunchKernelGGL((k_hexconv_mfma<TI, TO, 2>), grid, blk, 0, st, (const TI*)x, k, b, (TO*)y, G); \

@@ -16,6 +16,9 @@
 // d input is a gather (one thread per input pixel, no atomics, deterministic).  d W
 // and d bias are reductions over B*ho*wo samples: per-thread partial sums, a block
 // reduction, then one float atomic per (o, ci, tap) per block.
+// These are the generic kernels (any radius, stride, dilation, groups, padding mode, fp64):
+// wide dense radius-2 layers are routed, gradient by gradient, to the matrix-core kernels of
+// conv_mfma_bwd.hip first (conv_bwd_route; hg_hexconv2d_backward_plan tells which).
 #include <algorithm>
 #include <climits>
 
@@ -118,7 +121,7 @@ __global__ __launch_bounds__(BW_THREADS) void k_hexconv_bwd_weight(const Tx* __r
     const int64_t g = o / G.og;
     const int64_t total = G.B * G.ho * G.wo;
     const int64_t Wp = G.w + 2 * G.p;
-    const int nj = min(BW_NACC, G.cg * G.K - j0);
+    const int nj = dk ? min(BW_NACC, G.cg * G.K - j0) : 0;   // no d kernel: the bias alone
     const A padv = (A)G.pad_value;
     A acc[BW_NACC];
 #pragma unroll
@@ -173,6 +176,30 @@ __global__ __launch_bounds__(BW_THREADS) void k_hexconv_bwd_weight(const Tx* __r
     }
 }
 
+// conv_mfma_bwd.hip: the matrix-core kernels of wide dense radius-2 layers
+void conv_bwd_route(int x_dtype, int w_dtype, int64_t B, int64_t C, int64_t O, int64_t h,
+                    int64_t w, int64_t ho, int64_t wo, int radius, int stride, int padding,
+                    int dilation, int groups, int pad_mode, int* dx_kernel, int* dw_kernel);
+int conv_mfma_bwd_weight(const void* x, const float* gy, float* dk, float* db, int x_dtype,
+                         int64_t B, int64_t C, int64_t O, int64_t h, int64_t w, int padding,
+                         int off, int pad_mode, double pad_value, hipStream_t st);
+int conv_mfma_bwd_input(const float* kern, const float* gy, void* dx, int x_dtype, int64_t B,
+                        int64_t C, int64_t O, int64_t h, int64_t w, int64_t ho, int64_t wo,
+                        int padding, int off, hipStream_t st);
+
+// Argument checks of the backward (and of its plan query), in the order the call reports them
+static int bwd_check(int64_t batch, int64_t C, int64_t O, int64_t h, int64_t w, int radius,
+                     int stride, int padding, int dilation, int groups, int pad_mode,
+                     int w_dtype, int64_t* ho, int64_t* wo) {
+    int st = conv_out_shape(h, w, radius, stride, padding, dilation, ho, wo);
+    if (st) return st;
+    st = conv_check_args(batch, C, O, h, w, groups, padding, pad_mode);
+    if (st) return st;
+    if (3 * radius * radius - 3 * radius + 1 > BW_MAXK) return HG_EUNSUP;
+    if (w_dtype != HG_F32 && w_dtype != HG_F64) return HG_EDTYPE;
+    return HG_OK;
+}
+
 template <typename Tx, typename A>
 static int bwd_launch(const void* x, const void* kern, const void* gy, void* dx, void* dk,
                       void* db, const BwdGeom& G, hipStream_t st) {
@@ -204,7 +231,7 @@ static int bwd_launch(const void* x, const void* kern, const void* gy, void* dx,
         for (int pss = 0; pss < passes; ++pss) {
             hipLaunchKernelGGL((k_hexconv_bwd_weight<Tx, A>), grid, dim3(BW_THREADS), 0, st,
                                (const Tx*)x, (const A*)gy, dk ? (A*)dk : nullptr, (A*)db, G,
-                               dk ? pss * BW_NACC : nj);
+                               pss * BW_NACC);
             const int rc = launch_status();
             if (rc) return rc;
         }
@@ -222,13 +249,10 @@ extern "C" int hg_hexconv2d_backward(const void* x, const void* kernel, const vo
                                      double pad_value, void* stream) {
     using namespace hg;
     BwdGeom G;
-    int st = conv_out_shape(h, w, radius, stride, padding, dilation, &G.ho, &G.wo);
-    if (st) return st;
-    st = conv_check_args(batch, in_channels, out_channels, h, w, groups, padding, pad_mode);
+    const int st = bwd_check(batch, in_channels, out_channels, h, w, radius, stride, padding,
+                             dilation, groups, pad_mode, w_dtype, &G.ho, &G.wo);
     if (st) return st;
     G.K = 3 * radius * radius - 3 * radius + 1;
-    if (G.K > BW_MAXK) return HG_EUNSUP;
-    if (w_dtype != HG_F32 && w_dtype != HG_F64) return HG_EDTYPE;
     if (dx && !dtype_is_float(x_dtype)) return HG_EDTYPE;
     if (batch == 0 || G.ho == 0 || G.wo == 0) {
         // no samples: zero gradients (the reference's empty sums)
@@ -252,10 +276,46 @@ extern "C" int hg_hexconv2d_backward(const void* x, const void* kernel, const vo
     G.pad_mode = pad_mode;
     G.pad_value = pad_value;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // wide dense radius-2 layers: each gradient on its matrix-core kernel where it has one
+    int dxk, dwk;
+    conv_bwd_route(x_dtype, w_dtype, batch, in_channels, out_channels, h, w, G.ho, G.wo, radius,
+                   stride, padding, dilation, groups, pad_mode, &dxk, &dwk);
+    if (dx && dxk == HG_CONV_BWD_MFMA) {
+        const int rc = conv_mfma_bwd_input((const float*)kernel, (const float*)gy, dx, x_dtype,
+                                           batch, in_channels, out_channels, h, w, G.ho, G.wo,
+                                           padding, even_odd_offset & 1, s);
+        if (rc) return rc;
+        dx = nullptr;
+    }
+    if (dkernel && dwk == HG_CONV_BWD_MFMA) {
+        const int rc = conv_mfma_bwd_weight(x, (const float*)gy, (float*)dkernel, (float*)dbias,
+                                            x_dtype, batch, in_channels, out_channels, h, w,
+                                            padding, even_odd_offset & 1, pad_mode, pad_value, s);
+        if (rc) return rc;
+        dkernel = dbias = nullptr;
+    }
+    if (!dx && !dkernel && !dbias) return HG_OK;
     if (w_dtype == HG_F64) {
         HG_DISPATCH_IN(x_dtype, TX, { return bwd_launch<TX, double>(x, kernel, gy, dx, dkernel, dbias, G, s); });
     } else {
         HG_DISPATCH_IN(x_dtype, TX, { return bwd_launch<TX, float>(x, kernel, gy, dx, dkernel, dbias, G, s); });
     }
     return HG_EDTYPE;
+}
+
+extern "C" int hg_hexconv2d_backward_plan(int x_dtype, int w_dtype, int64_t batch,
+                                          int64_t in_channels, int64_t out_channels, int64_t h,
+                                          int64_t w, int radius, int stride, int padding,
+                                          int dilation, int groups, int pad_mode, int* dx_kernel,
+                                          int* dw_kernel) {
+    using namespace hg;
+    if (!dx_kernel || !dw_kernel) return HG_EINVAL;
+    int64_t ho, wo;
+    const int st = bwd_check(batch, in_channels, out_channels, h, w, radius, stride, padding,
+                             dilation, groups, pad_mode, w_dtype, &ho, &wo);
+    if (st) return st;
+    if (dtype_size(x_dtype) == 0) return HG_EDTYPE;
+    conv_bwd_route(x_dtype, w_dtype, batch, in_channels, out_channels, h, w, ho, wo, radius,
+                   stride, padding, dilation, groups, pad_mode, dx_kernel, dw_kernel);
+    return HG_OK;
 }

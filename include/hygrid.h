@@ -193,12 +193,33 @@ int hg_hexconv2d_epilogue(const void* x, const void* kernel, const void* bias, v
  * w_dtype, or NULL; dbias: (O,) of w_dtype, or NULL.  Outputs are overwritten.
  * x is read only for dkernel, kernel only for dx.  d kernel / d bias are sums
  * over B*ho*wo samples accumulated with float atomics (run-to-run last-bit
- * differences, as torch's own conv weight gradients). */
+ * differences, as torch's own conv weight gradients).
+ * Dense radius-2, stride-1, dilation-1 layers with float32 weights, padding 0..2 and x of
+ * F16 / BF16 / F32 run on the f32 matrix cores (conv_mfma_bwd.hip), each gradient routed on
+ * its own: d kernel (with d bias) when out_channels >= 16, d input when in_channels >= 16 and
+ * the padding is constant.  Everything else, and every call with the environment variable
+ * HYGRID_CONV_BWD_MFMA=0, runs the generic kernels.  d input is bit-reproducible on both. */
 int hg_hexconv2d_backward(const void* x, const void* kernel, const void* gy, void* dx,
                           void* dkernel, void* dbias, int x_dtype, int w_dtype, int64_t batch,
                           int64_t in_channels, int64_t out_channels, int64_t h, int64_t w,
                           int radius, int stride, int padding, int dilation, int groups,
                           int even_odd_offset, int pad_mode, double pad_value, void* stream);
+
+/* Which kernel hg_hexconv2d_backward would run for each gradient of this layer (nothing is
+ * launched, no device is touched): *dx_kernel for d input, *dw_kernel for d kernel (+ d bias;
+ * d bias asked for alone always takes the generic pass).  The same conditions as the call
+ * itself, HYGRID_CONV_BWD_MFMA included, answered for 16-byte-aligned buffers (alignment
+ * selects load widths inside a kernel, never the kernel).  Returns the negative status
+ * hg_hexconv2d_backward would return for bad arguments. */
+enum hg_conv_bwd_kernel { HG_CONV_BWD_GENERIC = 0, HG_CONV_BWD_MFMA = 1 };
+/* An answer slot of a host-only query: the address of an int in HOST memory (an `int*`; pass
+ * `&k`).  Its own type, so that a declaration says the library never writes device memory
+ * through it: every plain non-const pointer in this header is a buffer a kernel may write. */
+typedef int* hg_host_int_out;
+int hg_hexconv2d_backward_plan(int x_dtype, int w_dtype, int64_t batch, int64_t in_channels,
+                               int64_t out_channels, int64_t h, int64_t w, int radius,
+                               int stride, int padding, int dilation, int groups, int pad_mode,
+                               hg_host_int_out dx_kernel, hg_host_int_out dw_kernel);
 
 /* Hex raster storage formats (pure memory permutes; any element size 1/2/4/8).
  * hg_hex_to_type1: (planes, h, w) offset-row hex image -> (planes, h*row_repeat, 2w+1)
