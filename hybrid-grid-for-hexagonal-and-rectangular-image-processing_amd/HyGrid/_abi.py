@@ -28,6 +28,7 @@ HG_OP_RECT_TO_HEX, HG_OP_HEX_TO_RECT, HG_OP_HEXRESIZE = 0, 1, 2
 HG_KERNEL_GENERAL, HG_KERNEL_NEAREST, HG_KERNEL_STREAM, HG_KERNEL_DOWN, HG_KERNEL_UP = range(5)
 HG_PYR_FUSED, HG_PYR_FUSED_SHORT, HG_PYR_STREAM, HG_PYR_LDS = range(4)
 HG_CONV_BWD_GENERIC, HG_CONV_BWD_MFMA = 0, 1
+HG_CONV_FWD_OTHER, HG_CONV_FWD_MFMA_F32, HG_CONV_FWD_MFMA_BF16, HG_CONV_FWD_MFMA_BF16_DMA = range(4)
 HG_OK, HG_EINVAL, HG_EDTYPE, HG_ESHAPE, HG_EUNSUP, HG_EOVERFLOW = 0, -1, -2, -3, -4, -5
 PAD_MODES = {"constant": 0, "zeros": 0, "reflect": 1, "replicate": 2, "circular": 3}
 HG_ACT_NONE, HG_ACT_RELU, HG_ACT_LEAKY_RELU, HG_ACT_RELU6, HG_ACT_SIGMOID, HG_ACT_TANH = range(6)
@@ -68,6 +69,8 @@ SIGNATURES = {
                               _int),
     "hg_hexconv2d_backward_plan": ([_int, _int] + [_i64] * 5 + [_int] * 6
                                    + [ctypes.POINTER(_int)] * 2, _int),
+    "hg_hexconv2d_forward_plan": ([_int, _int, _int] + [_i64] * 5 + [_int] * 7 + [_dbl]
+                                  + [ctypes.POINTER(_int)], _int),
     "hg_hex_to_type1": ([_vp, _vp, _int] + [_i64] * 3 + [_int, _int, _vp], _int),
     "hg_strided_copy2d": ([_vp, _vp, _int] + [_i64] * 9 + [_vp], _int),
     "hg_hex_homography": ([_vp, _vp, _int, _int] + [_i64] * 5 + [_vp] * 3 + [_int, _vp], _int),

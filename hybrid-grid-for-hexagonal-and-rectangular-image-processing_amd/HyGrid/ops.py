@@ -420,6 +420,29 @@ def hexconv2d_backward_plan(x_dtype, w_dtype, batch, in_channels, out_channels, 
     return dxk.value, dwk.value
 
 
+def hexconv2d_forward_plan(x_dtype, w_dtype, y_dtype, batch, in_channels, out_channels, h, w,
+                           radius, stride=1, padding=0, dilation=1, groups=1, even_odd_offset=0,
+                           padding_mode="constant", padding_value=0.0):
+    """Which wide-channel kernel hexconv2d would run for this layer (hg_hexconv2d_forward_plan):
+    _abi.HG_CONV_FWD_MFMA_F32, _MFMA_BF16, _MFMA_BF16_DMA, or _abi.HG_CONV_FWD_OTHER (the
+    streaming or generic kernels), the HYGRID_CONV_MFMA* / HYGRID_CONV_DMA switches included.
+    Answered for a 16-byte-aligned x (a less than 4-byte-aligned bf16 x runs _MFMA_BF16 where
+    this says _DMA).  Nothing is launched and no device is needed.  dtypes: torch dtypes or
+    hg_dtype codes."""
+    pm = _abi.PAD_MODES.get(padding_mode)
+    if pm is None:
+        raise ValueError(f"unsupported padding_mode {padding_mode!r}")
+    xd, wd, yd = (d if isinstance(d, int) else _abi.dtype_code(d)
+                  for d in (x_dtype, w_dtype, y_dtype))
+    kern = ctypes.c_int()
+    st = _abi.lib().hg_hexconv2d_forward_plan(
+        xd, wd, yd, int(batch), int(in_channels), int(out_channels), int(h), int(w), int(radius),
+        int(stride), int(padding), int(dilation), int(groups), int(even_odd_offset), pm,
+        float(padding_value), ctypes.byref(kern))
+    _abi.check(st, "hg_hexconv2d_forward_plan")
+    return kern.value
+
+
 def hex_to_type1(x, even_odd_offset, row_repeat=1, out_dtype=None):
     """Offset-row hex raster (..., H, W) -> type1 (..., H*row_repeat, 2W+1) on the GPU
     (hg_hex_to_type1): row_repeat 1 = HexFrames.heximage_to_type1 (HexFrames.py:417-445),

@@ -22,6 +22,17 @@ constexpr int CM_PP = 72;                   // staged P pitch: 64 + tap column s
 constexpr int CM_CST = CM_PR * CM_PP;       // P channel stride
 constexpr int CM_WST = 7 * CM_OMAX + 16;    // weight channel stride (= 16 mod 32 banks)
 
+
+// Stride 2 (forward only): a workgroup's 4 x 64 outputs read staged rows 2 r0 .. 2 r0 + 8 and
+// staged columns 2 q0 + mink + (0..129).  Each staged row is kept as two column-parity planes:
+// sample column j sits in plane j & 1 at slot j >> 1, so the 16 columns 2 q + dk of a B fragment
+// (dk fixed within a tap and row parity) are 16 consecutive slots, as at stride 1.
+constexpr int CS_PR = 2 * (CM_ROWS - 1) + 3;    // staged P rows (wave wv reads rows 2 wv + dy, dy <= 2)
+constexpr int CS_SL = CM_Q + 1;                 // slots per plane in use (dk <= 3: slot q + 1)
+constexpr int CS_PL = 72;                       // plane pitch
+constexpr int CS_PP = 2 * CS_PL;                // row pitch; 9 * 144 = 1296 = 16 mod 32 banks
+constexpr int CS_CST = CS_PR * CS_PP;           // P channel stride
+
 typedef float cm_f4 __attribute__((ext_vector_type(4)));
 
 struct MfmaGeom {
@@ -47,27 +58,33 @@ inline bool conv_mfma_size_ok(int64_t C, int64_t O, int64_t h, int64_t w) {
     return C * h * w * 4 < ((int64_t)1 << 31);
 }
 
-// The forward geometry of a dense radius-2, stride-1, dilation-1 layer: shapes, tap tables,
-// staged frame, row / column tile counts (nto is the caller's: it picks the tile count per
-// workgroup).  false when the layer has no output or its taps do not fit the staged tile.
+// The forward geometry of a dense radius-2, dilation-1 layer of stride 1 or 2: shapes, tap
+// tables, staged frame, row / column tile counts (nto is the caller's: it picks the tile count
+// per workgroup).  false when the layer has no output or its taps do not fit the staged tile
+// (stride 1: 6 rows x CM_PP columns; stride 2: CS_PR rows x 2 planes of CS_SL slots).
 inline bool conv_mfma_forward_geom(MfmaGeom& G, int64_t B, int64_t C, int64_t O, int64_t h,
                                    int64_t w, int padding, int off, int pad_mode,
-                                   double pad_value) {
+                                   double pad_value, int stride = 1) {
     G.B = B; G.C = (int)C; G.O = (int)O; G.h = (int)h; G.w = (int)w; G.p = padding;
     G.pad_mode = pad_mode; G.pad_value = (float)pad_value;
     G.oy = G.ox = padding; G.Hp = G.h + 2 * padding; G.Wp = G.w + 2 * padding;
     int64_t ho, wo;
-    if (conv_out_shape(h, w, 2, 1, padding, 1, &ho, &wo)) return false;
+    if (stride != 1 && stride != 2) return false;
+    if (conv_out_shape(h, w, 2, stride, padding, 1, &ho, &wo)) return false;
     G.ho = (int)ho; G.wo = (int)wo;
     const int op = (off + padding) & 1;
-    int mink = INT_MAX, maxk = INT_MIN;
+    int mink = INT_MAX, maxk = INT_MIN, maxdy = 0;
     int dyv[7], dk0[7], dk1[7];
     for (int t = 0; t < 7; ++t) {
-        tap_geom(2, 1, 1, op, t, &dyv[t], &dk0[t], &dk1[t]);
+        tap_geom(2, stride, 1, op, t, &dyv[t], &dk0[t], &dk1[t]);
         mink = std::min(mink, std::min(dk0[t], dk1[t]));
         maxk = std::max(maxk, std::max(dk0[t], dk1[t]));
+        maxdy = std::max(maxdy, dyv[t]);
     }
-    if (maxk - mink + CM_Q > CM_PP) return false;
+    if (stride == 1 && maxk - mink + CM_Q > CM_PP) return false;
+    if (stride == 2 && (mink < 0 || 2 * (CM_Q - 1) + (maxk - mink) >= 2 * CS_SL ||
+                        2 * (CM_ROWS - 1) + maxdy >= CS_PR))
+        return false;
     G.mink = mink;
     for (int t = 0; t < 7; ++t) {
         G.dy[t] = dyv[t];
@@ -107,10 +124,19 @@ __device__ __forceinline__ void cm_stage_p(float* __restrict__ ps, const Tin* __
     }
 }
 
+// Which wide-channel forward kernel hg_hexconv2d runs for a layer whose arguments passed its
+// checks (enum hg_conv_fwd_kernel; HG_CONV_FWD_OTHER: none of them, the call goes on to the
+// generic kernels).  Host only; the one statement of the conditions, the env switches
+// HYGRID_CONV_MFMA / _MFMA_BF16 / _DMA included: conv_mfma_try launches from it and
+// hg_hexconv2d_forward_plan reports it.  x_align: the low bits of x's address (0 for the query).
+int conv_fwd_route(int x_dtype, int w_dtype, int y_dtype, int64_t B, int64_t C, int64_t O,
+                   int64_t h, int64_t w, int radius, int stride, int padding, int dilation,
+                   int groups, int off, int pad_mode, double pad_value, unsigned x_align);
+
 // Launches k_hexconv_mfma<x_dtype, y_dtype, nt> (the f32-MFMA forward kernel, nt = 2 or 4
-// output-channel tiles per workgroup) on a complete geometry; HG_EUNSUP for a dtype pair it
-// does not have.  conv_mfma.hip.
+// output-channel tiles per workgroup; stride 2: k_hexconv_mfma_s2) on a complete geometry of
+// that stride; HG_EUNSUP for a dtype pair it does not have.  conv_mfma.hip.
 int conv_mfma_launch_f32(const void* x, const float* k, const float* b, void* y, int x_dtype,
-                         int y_dtype, const MfmaGeom& G, int nt, hipStream_t st);
+                         int y_dtype, const MfmaGeom& G, int nt, hipStream_t st, int stride = 1);
 
 }  // namespace hg

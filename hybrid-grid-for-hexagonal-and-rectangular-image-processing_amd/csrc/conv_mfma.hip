@@ -623,77 +623,437 @@ void k_hexconv_mfma_bf16d(const __bf16* __restrict__ x,
         }
 }
 
-// Runs the MFMA kernel when it covers the call and pays (dense radius-2, stride-1,
-// dilation-1 conv with O >= 16, f32 weights); HG_EUNSUP otherwise.  Narrow inputs (C < 8: the
+// ---- stride 2 ------------------------------------------------------------------------------
+// The same GEMMs on a tile that walks the input at twice the output pitch: wave wv's output
+// row r0 + wv reads staged rows 2 wv + dy_t, output column q reads staged column 2 (q - q0) +
+// dk_t.  Rows are staged as two column-parity planes (conv_mfma.h), so a tap's B fragment is
+// 16 consecutive LDS slots of plane dk & 1 starting at slot (dk >> 1) + li, and the fragment
+// maps, the weight layouts, the accumulators and the epilogues are the stride-1 kernels'.
+// Sibling kernels, not a stride template argument: the stride-1 kernels keep their symbols.
+//
+// Input channels per LDS chunk of k_hexconv_mfma_s2: 4 (20.7 KB of P + 7.4 KB of weights = 28.2 KB,
+// 3-4 waves per SIMD) against 8 (56.3 KB, 2 workgroups per CU): 4.55 against 5.90 ms on
+// 64 -> 128 1080p b4 f32, 0.264 / 0.397 ms on the 3 -> 64 stem, 0.230 / 0.346 ms on 16 -> 16
+// 540p b8, 2.40 / 3.07 ms on 128 -> 256 540p b2 (profiles/conv_mfma_stride2_ab.txt): as at
+// stride 1, occupancy, not barrier count, is what the staging latency needs.
+#ifndef CS_CC
+#define CS_CC 4
+#endif
+static_assert(CS_CC % 4 == 0 && CS_CC <= CM_CC, "chunk: whole MFMA k quads, the weight stride's rows");
+#ifndef CS_PLANES
+#define CS_PLANES 1                          // 0 (A/B build): k_hexconv_mfma_s2 keeps a staged row's
+#endif                                       // columns in their natural order, stride-2 B reads
+
+__device__ __forceinline__ int cs_slot(int row, int dk) {     // staged (row, column 2 q' + dk) at q' = 0
+    return row * CS_PP + (dk & 1) * CS_PL + (dk >> 1);
+}
+
+// Stage P rows 2 r0 .. 2 r0 + 8 (staged frame), columns 2 q0 + mink + (0..129), of channels
+// c0 .. c0+CS_CC-1 as fp32 [c][row][plane][slot].  195 threads = 65 slots x 3 row phases; a
+// thread owns the two columns of its slot (their source indices computed once, cm_stage_p's
+// padding rules) and walks rows pr = phase, phase + 3, ... of every channel of the chunk.
+template <typename Tin>
+__device__ __forceinline__ void cs_stage_p(float* __restrict__ ps, const Tin* __restrict__ xb,
+                                           const MfmaGeom& G, int c0, int q0, int r0, int tid) {
+    if (tid < 3 * CS_SL) {
+        const int sl = tid % CS_SL, ph = tid / CS_SL;
+        const int px = 2 * q0 + G.mink + 2 * sl;          // plane 0's column; plane 1's is px + 1
+        const bool z0 = px >= G.Wp, z1 = px + 1 >= G.Wp;  // type1 structural zero columns
+        const int64_t x0 = z0 ? -1 : pad_map(px - G.ox, G.w, G.pad_mode);
+        const int64_t x1 = z1 ? -1 : pad_map(px + 1 - G.ox, G.w, G.pad_mode);
+#pragma unroll 4
+        for (int rr = ph; rr < CS_CC * CS_PR; rr += 3) {
+            const int cc = rr / CS_PR, pr = rr - cc * CS_PR;
+            const int c = c0 + cc, py = 2 * r0 + pr;
+            float v0 = 0.f, v1 = 0.f;
+            if (c < G.C && py < G.Hp) {
+                const int64_t yi = pad_map(py - G.oy, G.h, G.pad_mode);
+                const int64_t row = ((int64_t)c * G.h + yi) * G.w;
+                if (!z0) v0 = (yi < 0 || x0 < 0) ? G.pad_value : (float)xb[row + x0];
+                if (!z1) v1 = (yi < 0 || x1 < 0) ? G.pad_value : (float)xb[row + x1];
+            }
+            float* const d = ps + cc * CS_CST + pr * CS_PP + (CS_PLANES ? sl : 2 * sl);
+            d[0] = v0;
+            d[CS_PLANES ? CS_PL : 1] = v1;
+        }
+    }
+}
+
+template <typename Tin, typename Tout, int NOT>
+__global__ __launch_bounds__(CM_THREADS) void k_hexconv_mfma_s2(const Tin* __restrict__ x,
+                                                                   const float* __restrict__ kern,
+                                                                   const float* __restrict__ bias,
+                                                                   Tout* __restrict__ y, MfmaGeom G) {
+    __shared__ float ps[CS_CC * CS_CST];                 // P chunk [c][row][plane][slot]
+    __shared__ float ws[CS_CC * CM_WST];                 // weight chunk [c][t][o]
+    constexpr int CM_O = 16 * NOT;                       // output channels of this workgroup
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    unsigned bid = xcd_swizzle(blockIdx.x, gridDim.x);
+    const int tq = (int)(bid % G.ntq); bid /= G.ntq;
+    const int tr = (int)(bid % G.ntr); bid /= G.ntr;
+    const int to = (int)(bid % G.nto);
+    const int64_t b = bid / G.nto;
+    const int q0 = tq * CM_Q, r0 = tr * CM_ROWS, o0 = to * (16 * NOT);
+    const int r = r0 + wv;                               // this wave's output row
+    const int par = r & 1;
+    const int li = lane & 15, lk = lane >> 4;            // fragment row / k of this lane
+
+    constexpr bool TD = CM_TD && sizeof(Tout) == 2;      // 16-bit outputs: D as [column][channel]
+    cm_f4 acc[NOT][4];
+#pragma unroll
+    for (int ot = 0; ot < NOT; ++ot) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int o = o0 + ot * 16 + (TD ? li : lk * 4 + v);
+            const float bv = (bias && o < G.O) ? bias[o] : 0.f;
+#pragma unroll
+            for (int qt = 0; qt < 4; ++qt) acc[ot][qt][v] = bv;
+        }
+    }
+
+    const Tin* xb = x + b * (int64_t)G.C * G.h * G.w;
+    for (int c0 = 0; c0 < G.C; c0 += CS_CC) {
+        cs_stage_p(ps, xb, G, c0, q0, r0, tid);
+        // ---- stage weights W[o0 .. o0+CM_O-1][c0 .. c0+CS_CC-1][t] as [c][t][o] (k_hexconv_mfma's)
+        for (int e = tid; e < CM_O * (CS_CC * 7 / 4); e += CM_THREADS) {
+            const int o = e / (CS_CC * 7 / 4), f = e - o * (CS_CC * 7 / 4);
+            const int og = o0 + o;
+            float4 v4 = make_float4(0.f, 0.f, 0.f, 0.f);
+            const int64_t base = ((int64_t)og * G.C + c0) * 7 + 4 * f;   // first of 4 (c, t)
+            if (og < G.O) {
+                if (c0 + CS_CC <= G.C && (base & 3) == 0) {
+                    v4 = *reinterpret_cast<const float4*>(kern + base);
+                } else {
+                    float tmp[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int ct = 4 * f + j, c = c0 + ct / 7;
+                        tmp[j] = c < G.C ? kern[((int64_t)og * G.C + c) * 7 + ct % 7] : 0.f;
+                    }
+                    v4 = make_float4(tmp[0], tmp[1], tmp[2], tmp[3]);
+                }
+            }
+            const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int ct = 4 * f + j, cc = ct / 7, t = ct - cc * 7;
+                ws[cc * CM_WST + t * CM_O + o] = vv[j];
+            }
+        }
+        __syncthreads();
+        // ---- 7 taps x CS_CC / 4 channel quads x (NOT x 4) MFMAs -------------------------
+#pragma unroll
+        for (int t = 0; t < 7; ++t) {
+            const int dk = par ? G.dk[1][t] : G.dk[0][t];
+            const float* pb = CS_PLANES ? ps + lk * CS_CST + cs_slot(2 * wv + G.dy[t], dk) + li
+                                        : ps + lk * CS_CST + (2 * wv + G.dy[t]) * CS_PP + dk + 2 * li;
+            const float* wb = ws + lk * CM_WST + t * CM_O + li;
+#pragma unroll
+            for (int cq = 0; cq < CS_CC / 4; ++cq) {
+                float af[NOT], bf[4];
+#pragma unroll
+                for (int ot = 0; ot < NOT; ++ot) af[ot] = wb[cq * 4 * CM_WST + ot * 16];
+#pragma unroll
+                for (int qt = 0; qt < 4; ++qt) bf[qt] = pb[cq * 4 * CS_CST + qt * (CS_PLANES ? 16 : 32)];
+#pragma unroll
+                for (int ot = 0; ot < NOT; ++ot)
+#pragma unroll
+                    for (int qt = 0; qt < 4; ++qt)
+                        acc[ot][qt] = TD ? __builtin_amdgcn_mfma_f32_16x16x4f32(bf[qt], af[ot], acc[ot][qt], 0, 0, 0)
+                                            : __builtin_amdgcn_mfma_f32_16x16x4f32(af[ot], bf[qt], acc[ot][qt], 0, 0, 0);
+            }
+        }
+        __syncthreads();
+    }
+
+    if (r >= G.ho) return;
+    Tout* yb = y + b * (int64_t)G.O * G.ho * G.wo;
+    if constexpr (TD) {
+        cm_store_cols<Tout, NOT, 4>(acc, yb, G, o0 + li, q0 + lk * 4, r);
+        return;
+    }
+#pragma unroll
+    for (int ot = 0; ot < NOT; ++ot)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int o = o0 + ot * 16 + lk * 4 + v;
+            if (o >= G.O) continue;
+#pragma unroll
+            for (int qt = 0; qt < 4; ++qt) {
+                const int q = q0 + qt * 16 + li;
+                if (q >= G.wo) continue;
+                float val = acc[ot][qt][v];
+                if (G.epi.on) val = epi_apply(val, o, G.epi);
+                yb[((int64_t)o * G.ho + r) * G.wo + q] = (Tout)val;
+            }
+        }
+}
+
+constexpr int CSB_PSZ = CS_PR * CS_PP + 1;   // bf16 P fragments per chunk (+1: the zero fragment)
+
+// k_hexconv_mfma_bf16 at stride 2: register-staged P fragments [row][plane][slot] of the 8
+// channels, the same weight split and fragment layout.
+template <typename Tout, int NOT>
+__global__ __launch_bounds__(CM_THREADS) void k_hexconv_mfma_bf16_s2(const __bf16* __restrict__ x,
+                                                                     const float* __restrict__ kern,
+                                                                     const float* __restrict__ bias,
+                                                                     Tout* __restrict__ y, MfmaGeom G) {
+    constexpr int CM_O = 16 * NOT;
+    __shared__ cm_u4 psb[CSB_PSZ];
+    __shared__ cm_u4 wsb[3 * 2 * CM_O * 4];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    unsigned bid = xcd_swizzle(blockIdx.x, gridDim.x);
+    const int tq = (int)(bid % G.ntq); bid /= G.ntq;
+    const int tr = (int)(bid % G.ntr); bid /= G.ntr;
+    const int to = (int)(bid % G.nto);
+    const int64_t b = bid / G.nto;
+    const int q0 = tq * CM_Q, r0 = tr * CM_ROWS, o0 = to * CM_O;
+    const int r = r0 + wv;
+    const int par = r & 1;
+    const int Wp = G.w + 2 * G.p, Hp = G.h + 2 * G.p;
+    const int li = lane & 15, lg = lane >> 4;            // fragment row / column, k group
+    const unsigned short padv = __builtin_bit_cast(unsigned short, (__bf16)G.pad_value);
+
+    constexpr bool TD = CM_TD && sizeof(Tout) == 2;      // 16-bit outputs: D as [column][channel]
+    cm_f4 acc[NOT][4];
+#pragma unroll
+    for (int ot = 0; ot < NOT; ++ot) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int o = o0 + ot * 16 + (TD ? li : lg * 4 + v);
+            const float bv = (bias && o < G.O) ? bias[o] : 0.f;
+#pragma unroll
+            for (int qt = 0; qt < 4; ++qt) acc[ot][qt][v] = bv;
+        }
+    }
+    if (tid == 0) psb[CSB_PSZ - 1] = cm_u4{0u, 0u, 0u, 0u};
+    // this lane's P fragment (per k block and column tile): tap t = 4 kb + lg, staged row
+    // 2 wv + dy_t, column 2 (qt * 16 + li) + dk_t; the 8th tap slot reads the zero fragment
+    int pidx[2];
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+        const int t = 4 * kb + lg;
+        pidx[kb] = t < 7 ? cs_slot(2 * wv + G.dy[t], par ? G.dk[1][t] : G.dk[0][t]) + li : -1;
+    }
+
+    const unsigned short* xb = reinterpret_cast<const unsigned short*>(x) + b * (int64_t)G.C * G.h * G.w;
+    for (int c0 = 0; c0 < G.C; c0 += CM_CC) {
+        // ---- stage P rows 2 r0 .. 2 r0+8, columns 2 q0 + mink + (0..129), 8 channels -----
+        // 195 threads = 65 slots x 3 row phases; a thread's two columns are its slot's planes
+        if (tid < 3 * CS_SL) {
+            const int sl = tid % CS_SL, ph = tid / CS_SL;
+            const int px = 2 * q0 + G.mink + 2 * sl;
+            const bool zc[2] = {px >= Wp, px + 1 >= Wp};     // type1 structural zero columns
+            const int64_t xi[2] = {zc[0] ? -1 : pad_map(px - G.p, G.w, G.pad_mode),
+                                   zc[1] ? -1 : pad_map(px + 1 - G.p, G.w, G.pad_mode)};
+            // one row (16 loads) in flight: unrolled, the 48 loads took 125 VGPRs and 2 waves per SIMD
+#pragma unroll 1
+            for (int k = 0; k < 3; ++k) {
+                const int pr = ph + 3 * k, py = 2 * r0 + pr;
+                const int64_t yi = py < Hp ? pad_map(py - G.p, G.h, G.pad_mode) : -1;
+#pragma unroll
+                for (int pl = 0; pl < 2; ++pl) {
+                    unsigned short v[8];
+#pragma unroll
+                    for (int cc = 0; cc < 8; ++cc) {
+                        const int c = c0 + cc;
+                        unsigned short e = 0;
+                        if (!zc[pl] && c < G.C && py < Hp)
+                            e = (yi < 0 || xi[pl] < 0) ? padv : xb[((int64_t)c * G.h + yi) * G.w + xi[pl]];
+                        v[cc] = e;
+                    }
+                    psb[pr * CS_PP + pl * CS_PL + sl] =
+                        cm_u4{v[0] | ((unsigned)v[1] << 16), v[2] | ((unsigned)v[3] << 16),
+                              v[4] | ((unsigned)v[5] << 16), v[6] | ((unsigned)v[7] << 16)};
+                }
+            }
+        }
+        // ---- stage the weights of taps (o, t), 8 channels, as 3 bf16 parts (k_hexconv_mfma_bf16's)
+        int ml = 0;
+        for (int e = tid; e < CM_O * 8; e += CM_THREADS) {
+            const int o = e >> 3, t = e & 7, og = o0 + o;
+            unsigned short h[8], m[8], l[8];
+#pragma unroll
+            for (int cc = 0; cc < 8; ++cc) {
+                const int c = c0 + cc;
+                const float wf = (t < 7 && og < G.O && c < G.C) ? kern[((int64_t)og * G.C + c) * 7 + t] : 0.f;
+                const __bf16 bh = (__bf16)wf;
+                const float r1 = wf - (float)bh;
+                const __bf16 bm = (__bf16)r1;
+                const __bf16 bl = (__bf16)(r1 - (float)bm);
+                h[cc] = __builtin_bit_cast(unsigned short, bh);
+                m[cc] = __builtin_bit_cast(unsigned short, bm);
+                l[cc] = __builtin_bit_cast(unsigned short, bl);
+                ml |= (m[cc] | l[cc]) & 0x7fff;              // a nonzero part (+-0 is zero)
+            }
+            const int kb = t >> 2, g = t & 3;
+            auto pk = [](const unsigned short* u) {
+                return cm_u4{u[0] | ((unsigned)u[1] << 16), u[2] | ((unsigned)u[3] << 16),
+                             u[4] | ((unsigned)u[5] << 16), u[6] | ((unsigned)u[7] << 16)};
+            };
+            wsb[((0 * 2 + kb) * CM_O + o) * 4 + cd_wslot(o, g)] = pk(h);
+            wsb[((1 * 2 + kb) * CM_O + o) * 4 + cd_wslot(o, g)] = pk(m);
+            wsb[((2 * 2 + kb) * CM_O + o) * 4 + cd_wslot(o, g)] = pk(l);
+        }
+        const int nparts = __syncthreads_or(ml != 0) ? 3 : 1;   // uniform per workgroup
+        // ---- 2 k blocks x 4 column tiles x 3 weight parts x NOT channel tiles -------------
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+            cm_b8 bf[4];
+#pragma unroll
+            for (int qt = 0; qt < 4; ++qt)
+                bf[qt] = __builtin_bit_cast(cm_b8, psb[pidx[kb] < 0 ? CSB_PSZ - 1 : pidx[kb] + qt * 16]);
+#pragma unroll
+            for (int pt = 0; pt < 3; ++pt) {
+                if (pt >= nparts) break;
+#pragma unroll
+                for (int ot = 0; ot < NOT; ++ot) {
+                    const cm_b8 af = __builtin_bit_cast(cm_b8, wsb[((pt * 2 + kb) * CM_O + ot * 16 + li) * 4 + cd_wslot(li, lg)]);
+#pragma unroll
+                    for (int qt = 0; qt < 4; ++qt)
+                        acc[ot][qt] = TD ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[qt], af, acc[ot][qt], 0, 0, 0)
+                                            : __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf[qt], acc[ot][qt], 0, 0, 0);
+                }
+            }
+        }
+        __syncthreads();
+    }
+
+    if (r >= G.ho) return;
+    Tout* yb = y + b * (int64_t)G.O * G.ho * G.wo;
+    if constexpr (TD) {
+        cm_store_cols<Tout, NOT, 4>(acc, yb, G, o0 + li, q0 + lg * 4, r);
+        return;
+    }
+#pragma unroll
+    for (int ot = 0; ot < NOT; ++ot)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int o = o0 + ot * 16 + lg * 4 + v;
+            if (o >= G.O) continue;
+#pragma unroll
+            for (int qt = 0; qt < 4; ++qt) {
+                const int q = q0 + qt * 16 + li;
+                if (q >= G.wo) continue;
+                float val = acc[ot][qt][v];
+                if (G.epi.on) val = epi_apply(val, o, G.epi);
+                yb[((int64_t)o * G.ho + r) * G.wo + q] = (Tout)val;
+            }
+        }
+}
+
+// Output-channel tiles per workgroup (A/B switch HYGRID_CONV_NT=2: two for any O)
+static int conv_mfma_nt(int64_t O) { return (O <= 32 || env_is("HYGRID_CONV_NT", "2")) ? 2 : 4; }
+
+constexpr int CS_MIN_O = 16;                 // stride 2: out_channels from which the MFMA kernels pay
+
+// Which wide-channel kernel takes the call (conv_mfma.h): dense radius-2, dilation-1 conv of
+// stride 1 or 2 with O >= 16, f32 weights, padding 0..2.  Narrow inputs (C < 8: the
 // 3-channel stem of a segmentation model, HexModules.py:97-288) run here too, their channel
 // chunk padded with zeros (staging and weights read 0 past C): HexConv2d(3 -> 64) 1080p b4
-// 2.76 -> 0.50 ms (bf16) and 2.84 -> 1.02 ms (f32) against the generic kernel, round 6,
-// profiles/r06/stem_conv_ab.txt.
-int conv_mfma_try(const void* x, const float* k, const float* b, void* y, int x_dtype,
-                  int y_dtype, int64_t B, int64_t C, int64_t O, int64_t h, int64_t w, int radius,
-                  int stride, int padding, int dilation, int groups, int off, int pad_mode,
-                  double pad_value, const Epilogue& epi, hipStream_t st) {
-    if (env_is("HYGRID_CONV_MFMA", "0")) return HG_EUNSUP;   // A/B switch: generic kernels
-    if (radius != 2 || stride != 1 || dilation != 1 || groups != 1) return HG_EUNSUP;
-    if (C < 1 || O < 16 || padding < 0 || padding > 2) return HG_EUNSUP;
-    if (!conv_mfma_size_ok(C, O, h, w)) return HG_EUNSUP;       // 32-bit buffer offsets
+// 2.76 -> 0.50 ms (bf16) and 2.84 -> 1.02 ms (f32) against the generic kernel at stride 1,
+// round 6, profiles/r06/stem_conv_ab.txt; stride 2: profiles/conv_mfma_stride2_ab.txt.
+int conv_fwd_route(int x_dtype, int w_dtype, int y_dtype, int64_t B, int64_t C, int64_t O,
+                   int64_t h, int64_t w, int radius, int stride, int padding, int dilation,
+                   int groups, int off, int pad_mode, double pad_value, unsigned x_align) {
+    if (env_is("HYGRID_CONV_MFMA", "0")) return HG_CONV_FWD_OTHER;   // A/B switch: generic kernels
+    if (w_dtype != HG_F32) return HG_CONV_FWD_OTHER;
+    if (radius != 2 || (stride != 1 && stride != 2) || dilation != 1 || groups != 1)
+        return HG_CONV_FWD_OTHER;
+    if (C < 1 || O < (stride == 2 ? CS_MIN_O : 16) || padding < 0 || padding > 2)
+        return HG_CONV_FWD_OTHER;
+    if (!conv_mfma_size_ok(C, O, h, w)) return HG_CONV_FWD_OTHER;   // 32-bit buffer offsets
     MfmaGeom G = {};
-    if (!conv_mfma_forward_geom(G, B, C, O, h, w, padding, off, pad_mode, pad_value)) return HG_EUNSUP;
-    G.epi = epi;
-    // output-channel tiles per workgroup (A/B switch HYGRID_CONV_NT=2: two for any O)
-    const int nt = (G.O <= 32 || env_is("HYGRID_CONV_NT", "2")) ? 2 : 4;
-    G.nto = (G.O + 16 * nt - 1) / (16 * nt);
-    const int64_t blocks = B * (int64_t)G.ntq * G.ntr * G.nto;
-    if (blocks > INT_MAX || blocks == 0) return blocks == 0 ? HG_OK : HG_EUNSUP;
-    const dim3 grid((unsigned)blocks), blk(CM_THREADS);
+    if (!conv_mfma_forward_geom(G, B, C, O, h, w, padding, off, pad_mode, pad_value, stride))
+        return HG_CONV_FWD_OTHER;
+    const int nt = conv_mfma_nt(O);
+    const int64_t blocks = B * (int64_t)G.ntq * G.ntr * ((G.O + 16 * nt - 1) / (16 * nt));
+    if (blocks > INT_MAX || blocks <= 0) return HG_CONV_FWD_OTHER;
     // bf16 inputs: the split-weight bf16 kernel, when the pad value is a bf16 (the padded
     // input keeps the input's dtype, as F.pad does; anything else keeps the f32 kernel)
     const bool bf_pad = (double)(float)(__bf16)(float)pad_value == pad_value;
     // A/B switch HYGRID_CONV_MFMA_BF16=0: the f32 kernel
     if (x_dtype == HG_BF16 && bf_pad && !env_is("HYGRID_CONV_MFMA_BF16", "0") &&
         (y_dtype == HG_BF16 || y_dtype == HG_F32)) {
-        // LDS-DMA staging (A/B switch HYGRID_CONV_DMA=0: the register-staged kernel below):
-        // rows must be dword-aligned (even width, 4-B aligned base)
-        if (!env_is("HYGRID_CONV_DMA", "0") && (G.w % 2) == 0 && (reinterpret_cast<uintptr_t>(x) & 3) == 0) {
-            const int nch = (G.C + CM_CC - 1) / CM_CC, Opad = G.nto * 16 * nt;
-            const size_t wbytes = (size_t)nch * 6 * Opad * 64, fbytes = (size_t)nch * (Opad / 16) * 4;
-            void* ws = nullptr;
-            hipError_t e = hipMallocAsync(&ws, wbytes + fbytes, st);
-            if (e != hipSuccess) return (int)e;
-            cm_u4* wfr = static_cast<cm_u4*>(ws);
-            int* flg = reinterpret_cast<int*>(static_cast<char*>(ws) + wbytes);
-            hipLaunchKernelGGL(k_wsplit_bf16, dim3(nch, Opad / 16), dim3(128), 0, st, k, wfr, flg, G.C, G.O, Opad);
+        // LDS-DMA staging, stride 1 only (A/B switch HYGRID_CONV_DMA=0: the register-staged
+        // kernel): rows must be dword-aligned (even width, 4-B aligned base)
+        if (stride == 1 && !env_is("HYGRID_CONV_DMA", "0") && (w % 2) == 0 && (x_align & 3) == 0)
+            return HG_CONV_FWD_MFMA_BF16_DMA;
+        return HG_CONV_FWD_MFMA_BF16;
+    }
+    // the dtype pairs of conv_mfma_launch_f32
+    const bool pair = (x_dtype == HG_BF16 && (y_dtype == HG_BF16 || y_dtype == HG_F32)) ||
+                      (x_dtype == HG_F16 && (y_dtype == HG_F16 || y_dtype == HG_F32)) ||
+                      (x_dtype == HG_F32 && (y_dtype == HG_F32 || y_dtype == HG_BF16 || y_dtype == HG_F16));
+    return pair ? HG_CONV_FWD_MFMA_F32 : HG_CONV_FWD_OTHER;
+}
+
+// Runs the kernel conv_fwd_route names; HG_EUNSUP when that is none of this file's.
+int conv_mfma_try(const void* x, const float* k, const float* b, void* y, int x_dtype,
+                  int y_dtype, int64_t B, int64_t C, int64_t O, int64_t h, int64_t w, int radius,
+                  int stride, int padding, int dilation, int groups, int off, int pad_mode,
+                  double pad_value, const Epilogue& epi, hipStream_t st) {
+    const int route = conv_fwd_route(x_dtype, HG_F32, y_dtype, B, C, O, h, w, radius, stride, padding,
+                                     dilation, groups, off, pad_mode, pad_value,
+                                     (unsigned)(reinterpret_cast<uintptr_t>(x) & 15));
+    if (route == HG_CONV_FWD_OTHER) return HG_EUNSUP;
+    MfmaGeom G = {};
+    if (!conv_mfma_forward_geom(G, B, C, O, h, w, padding, off, pad_mode, pad_value, stride))
+        return HG_EUNSUP;
+    G.epi = epi;
+    const int nt = conv_mfma_nt(G.O);
+    G.nto = (G.O + 16 * nt - 1) / (16 * nt);
+    if (route == HG_CONV_FWD_MFMA_F32) return conv_mfma_launch_f32(x, k, b, y, x_dtype, y_dtype, G, nt, st, stride);
+    const int64_t blocks = B * (int64_t)G.ntq * G.ntr * G.nto;
+    const dim3 grid((unsigned)blocks), blk(CM_THREADS);
+    if (route == HG_CONV_FWD_MFMA_BF16_DMA) {
+        const int nch = (G.C + CM_CC - 1) / CM_CC, Opad = G.nto * 16 * nt;
+        const size_t wbytes = (size_t)nch * 6 * Opad * 64, fbytes = (size_t)nch * (Opad / 16) * 4;
+        void* ws = nullptr;
+        hipError_t e = hipMallocAsync(&ws, wbytes + fbytes, st);
+        if (e != hipSuccess) return (int)e;
+        cm_u4* wfr = static_cast<cm_u4*>(ws);
+        int* flg = reinterpret_cast<int*>(static_cast<char*>(ws) + wbytes);
+        hipLaunchKernelGGL(k_wsplit_bf16, dim3(nch, Opad / 16), dim3(128), 0, st, k, wfr, flg, G.C, G.O, Opad);
 #define HG_CD_LAUNCH2(TO, NT_)                                                                \
-            hipLaunchKernelGGL((k_hexconv_mfma_bf16d<TO, NT_>), grid, blk, 0, st, (const __bf16*)x, wfr, flg, b, (TO*)y, G, Opad);
+        hipLaunchKernelGGL((k_hexconv_mfma_bf16d<TO, NT_>), grid, blk, 0, st, (const __bf16*)x, wfr, flg, b, (TO*)y, G, Opad);
 #define HG_CD_LAUNCH(TO)                                                                      \
-            if (nt == 2) { HG_CD_LAUNCH2(TO, 2) } else { HG_CD_LAUNCH2(TO, 4) }
-            if (y_dtype == HG_BF16) { HG_CD_LAUNCH(__bf16) } else { HG_CD_LAUNCH(float) }
+        if (nt == 2) { HG_CD_LAUNCH2(TO, 2) } else { HG_CD_LAUNCH2(TO, 4) }
+        if (y_dtype == HG_BF16) { HG_CD_LAUNCH(__bf16) } else { HG_CD_LAUNCH(float) }
 #undef HG_CD_LAUNCH
 #undef HG_CD_LAUNCH2
-            const int ls = launch_status();
-            const hipError_t fe = hipFreeAsync(ws, st);
-            return ls != HG_OK ? ls : (int)fe;
-        }
-#define HG_CB_LAUNCH(TO)                                                                      \
-        if (nt == 2)                                                                          \
-            hipLaunchKernelGGL((k_hexconv_mfma_bf16<TO, 2>), grid, blk, 0, st, (const __bf16*)x, k, b, (TO*)y, G); \
-        else                                                                                  \
-            hipLaunchKernelGGL((k_hexconv_mfma_bf16<TO, 4>), grid, blk, 0, st, (const __bf16*)x, k, b, (TO*)y, G); \
-        return launch_status();
-        if (y_dtype == HG_BF16) { HG_CB_LAUNCH(__bf16) }
-        HG_CB_LAUNCH(float)
-#undef HG_CB_LAUNCH
+        const int ls = launch_status();
+        const hipError_t fe = hipFreeAsync(ws, st);
+        return ls != HG_OK ? ls : (int)fe;
     }
-    return conv_mfma_launch_f32(x, k, b, y, x_dtype, y_dtype, G, nt, st);
+#define HG_CB_LAUNCH(KN, TO)                                                                  \
+    if (nt == 2)                                                                              \
+        hipLaunchKernelGGL((KN<TO, 2>), grid, blk, 0, st, (const __bf16*)x, k, b, (TO*)y, G); \
+    else                                                                                      \
+        hipLaunchKernelGGL((KN<TO, 4>), grid, blk, 0, st, (const __bf16*)x, k, b, (TO*)y, G); \
+    return launch_status();
+    if (stride == 2) {
+        if (y_dtype == HG_BF16) { HG_CB_LAUNCH(k_hexconv_mfma_bf16_s2, __bf16) }
+        HG_CB_LAUNCH(k_hexconv_mfma_bf16_s2, float)
+    }
+    if (y_dtype == HG_BF16) { HG_CB_LAUNCH(k_hexconv_mfma_bf16, __bf16) }
+    HG_CB_LAUNCH(k_hexconv_mfma_bf16, float)
+#undef HG_CB_LAUNCH
 }
 
 int conv_mfma_launch_f32(const void* x, const float* k, const float* b, void* y, int x_dtype,
-                         int y_dtype, const MfmaGeom& G, int nt, hipStream_t st) {
+                         int y_dtype, const MfmaGeom& G, int nt, hipStream_t st, int stride) {
     const int64_t blocks = G.B * (int64_t)G.ntq * G.ntr * G.nto;
     if (blocks > INT_MAX || blocks <= 0) return blocks == 0 ? HG_OK : HG_EUNSUP;
     const dim3 grid((unsigned)blocks), blk(CM_THREADS);
 #define HG_CM_LAUNCH(TI, TO)                                                                  \
-    if (nt == 2)                                                                              \
+    if (stride == 2 && nt == 2)                                                               \
+        hipLaunchKernelGGL((k_hexconv_mfma_s2<TI, TO, 2>), grid, blk, 0, st, (const TI*)x, k, b, (TO*)y, G); \
+    else if (stride == 2)                                                                     \
+        hipLaunchKernelGGL((k_hexconv_mfma_s2<TI, TO, 4>), grid, blk, 0, st, (const TI*)x, k, b, (TO*)y, G); \
+    else if (nt == 2)                                                                         \
         hipLaunchKernelGGL((k_hexconv_mfma<TI, TO, 2>), grid, blk, 0, st, (const TI*)x, k, b, (TO*)y, G); \
     else                                                                                      \
         hipLaunchKernelGGL((k_hexconv_mfma<TI, TO, 4>), grid, blk, 0, st, (const TI*)x, k, b, (TO*)y, G); \

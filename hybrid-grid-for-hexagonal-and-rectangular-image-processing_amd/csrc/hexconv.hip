@@ -291,6 +291,30 @@ int conv_mfma_try(const void* x, const float* k, const float* b, void* y, int x_
                   int y_dtype, int64_t B, int64_t C, int64_t O, int64_t h, int64_t w, int radius,
                   int stride, int padding, int dilation, int groups, int off, int pad_mode,
                   double pad_value, const Epilogue& epi, hipStream_t st);   // conv_mfma.hip
+int conv_fwd_route(int x_dtype, int w_dtype, int y_dtype, int64_t B, int64_t C, int64_t O,
+                   int64_t h, int64_t w, int radius, int stride, int padding, int dilation,
+                   int groups, int off, int pad_mode, double pad_value,
+                   unsigned x_align);                                       // conv_mfma.hip
+
+// Argument checks of the forward (and of its plan query) that need no buffer, in the order the
+// call reports them; the dtype and size checks follow the empty-call return (fwd_check_rest)
+static int fwd_check(int64_t batch, int64_t C, int64_t O, int64_t h, int64_t w, int radius,
+                     int stride, int padding, int dilation, int groups, int pad_mode,
+                     int64_t* ho, int64_t* wo) {
+    int st = conv_out_shape(h, w, radius, stride, padding, dilation, ho, wo);
+    if (st) return st;
+    st = conv_check_args(batch, C, O, h, w, groups, padding, pad_mode);
+    if (st) return st;
+    if (3 * radius * radius - 3 * radius + 1 > CV_MAXK) return HG_EUNSUP;
+    return HG_OK;
+}
+
+static int fwd_check_rest(int w_dtype, int y_dtype, int64_t h, int64_t w, int64_t ho, int64_t wo) {
+    if (w_dtype != HG_F32 && w_dtype != HG_F64) return HG_EDTYPE;
+    if (!dtype_is_float(y_dtype)) return HG_EDTYPE;
+    if (h * w >= INT_MAX / 2 || ho * wo >= INT_MAX / 2) return HG_ESHAPE;
+    return HG_OK;
+}
 
 }  // namespace hg
 
@@ -327,6 +351,29 @@ int hg_hexconv2d_generic_plan(int w_dtype, int64_t batch, int64_t in_channels,
     return HG_OK;
 }
 
+int hg_hexconv2d_forward_plan(int x_dtype, int w_dtype, int y_dtype, int64_t batch,
+                              int64_t in_channels, int64_t out_channels, int64_t h, int64_t w,
+                              int radius, int stride, int padding, int dilation, int groups,
+                              int even_odd_offset, int pad_mode, double pad_value, int* kernel) {
+    using namespace hg;
+    if (!kernel) return HG_EINVAL;
+    int64_t ho, wo;
+    int st = fwd_check(batch, in_channels, out_channels, h, w, radius, stride, padding, dilation,
+                       groups, pad_mode, &ho, &wo);
+    if (st) return st;
+    if (batch == 0 || ho == 0 || wo == 0) {               // nothing would be launched
+        *kernel = HG_CONV_FWD_OTHER;
+        return HG_OK;
+    }
+    if (dtype_size(x_dtype) == 0) return HG_EDTYPE;
+    st = fwd_check_rest(w_dtype, y_dtype, h, w, ho, wo);
+    if (st) return st;
+    *kernel = conv_fwd_route(x_dtype, w_dtype, y_dtype, batch, in_channels, out_channels, h, w,
+                             radius, stride, padding, dilation, groups, even_odd_offset & 1,
+                             pad_mode, pad_value, 0u);
+    return HG_OK;
+}
+
 int hg_hexconv2d(const void* x, const void* kernel, const void* bias, void* y, int x_dtype,
                  int w_dtype, int y_dtype, int64_t batch, int64_t in_channels,
                  int64_t out_channels, int64_t h, int64_t w, int radius, int stride,
@@ -351,17 +398,14 @@ int hg_hexconv2d_epilogue(const void* x, const void* kernel, const void* bias, v
     epi.scale = scale; epi.shift = shift; epi.act = act; epi.slope = act_param;
     epi.on = (scale || shift || act != HG_ACT_NONE) ? 1 : 0;
     ConvGeom G;
-    int st = conv_out_shape(h, w, radius, stride, padding, dilation, &G.ho, &G.wo);
-    if (st) return st;
-    st = conv_check_args(batch, in_channels, out_channels, h, w, groups, padding, pad_mode);
+    int st = fwd_check(batch, in_channels, out_channels, h, w, radius, stride, padding, dilation,
+                       groups, pad_mode, &G.ho, &G.wo);
     if (st) return st;
     G.K = 3 * radius * radius - 3 * radius + 1;
-    if (G.K > CV_MAXK) return HG_EUNSUP;
     if (batch == 0 || G.ho == 0 || G.wo == 0) return HG_OK;
     if (!x || !kernel || !y) return HG_EINVAL;
-    if (w_dtype != HG_F32 && w_dtype != HG_F64) return HG_EDTYPE;
-    if (!dtype_is_float(y_dtype)) return HG_EDTYPE;
-    if (h * w >= INT_MAX / 2 || G.ho * G.wo >= INT_MAX / 2) return HG_ESHAPE;
+    st = fwd_check_rest(w_dtype, y_dtype, h, w, G.ho, G.wo);
+    if (st) return st;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (radius == 2 && stride == 1 && dilation == 1 && pad_mode == HG_PAD_CONSTANT &&
         w_dtype == HG_F32 && in_channels <= 3 && out_channels <= 3) {

@@ -162,7 +162,11 @@ int hg_hexconv2d_generic_plan(int w_dtype, int64_t batch, int64_t in_channels,
  * x: (B, C, h, w) of x_dtype; kernel: (O, C/groups, K) with K = 3r^2-3r+1 (the
  * reference parameter `kernel` [O, C/g, 1, K], :74) of w_dtype (F32 or F64);
  * bias: (O,) of w_dtype or NULL; y: (B, O, ho, wo) of y_dtype.
- * Accumulates in w_dtype, as the reference (`input.to(self.kernel.dtype)`, :107). */
+ * Accumulates in w_dtype, as the reference (`input.to(self.kernel.dtype)`, :107).
+ * Dense radius-2, dilation-1 layers of stride 1 or 2 with float32 weights, out_channels >= 16
+ * and padding 0..2 (any mode) run as an implicit GEMM on the matrix cores (conv_mfma.hip;
+ * hg_hexconv2d_forward_plan tells which kernel); everything else, and every call with the
+ * environment variable HYGRID_CONV_MFMA=0, runs the streaming or generic kernels. */
 int hg_hexconv2d(const void* x, const void* kernel, const void* bias, void* y, int x_dtype,
                  int w_dtype, int y_dtype, int64_t batch, int64_t in_channels,
                  int64_t out_channels, int64_t h, int64_t w, int radius, int stride,
@@ -220,6 +224,28 @@ int hg_hexconv2d_backward_plan(int x_dtype, int w_dtype, int64_t batch, int64_t 
                                int64_t out_channels, int64_t h, int64_t w, int radius,
                                int stride, int padding, int dilation, int groups, int pad_mode,
                                hg_host_int_out dx_kernel, hg_host_int_out dw_kernel);
+
+/* Which wide-channel kernel hg_hexconv2d / hg_hexconv2d_epilogue would run for this layer
+ * (nothing is launched, no device is touched): *kernel is HG_CONV_FWD_MFMA_F32
+ * (k_hexconv_mfma, stride 2: k_hexconv_mfma_s2; f32 / f16 inputs, and bf16 inputs whose pad
+ * value is not a bf16), HG_CONV_FWD_MFMA_BF16 (k_hexconv_mfma_bf16, stride 2:
+ * k_hexconv_mfma_bf16_s2; bf16 inputs, register-staged), HG_CONV_FWD_MFMA_BF16_DMA
+ * (k_hexconv_mfma_bf16d; bf16 inputs of even width, stride 1 only), or HG_CONV_FWD_OTHER when
+ * the call goes to the streaming or generic kernels.  The same host function routes the real
+ * call, the switches HYGRID_CONV_MFMA, HYGRID_CONV_MFMA_BF16 and HYGRID_CONV_DMA included.
+ * The query has no x, so it answers for a 16-byte-aligned x: at stride 1 the DMA kernel needs
+ * a 4-byte-aligned x, and a real call with a less aligned one (a sliced bf16 view) runs
+ * HG_CONV_FWD_MFMA_BF16 where the query said _DMA; nothing else depends on alignment.
+ * Returns the negative status hg_hexconv2d would return for bad arguments (*kernel is then
+ * left alone). */
+enum hg_conv_fwd_kernel { HG_CONV_FWD_OTHER = 0,        /* streaming or generic kernels */
+                          HG_CONV_FWD_MFMA_F32 = 1, HG_CONV_FWD_MFMA_BF16 = 2,
+                          HG_CONV_FWD_MFMA_BF16_DMA = 3 };
+int hg_hexconv2d_forward_plan(int x_dtype, int w_dtype, int y_dtype, int64_t batch,
+                              int64_t in_channels, int64_t out_channels, int64_t h, int64_t w,
+                              int radius, int stride, int padding, int dilation, int groups,
+                              int even_odd_offset, int pad_mode, double pad_value,
+                              hg_host_int_out kernel);
 
 /* Hex raster storage formats (pure memory permutes; any element size 1/2/4/8).
  * hg_hex_to_type1: (planes, h, w) offset-row hex image -> (planes, h*row_repeat, 2w+1)
