@@ -26,6 +26,7 @@ HG_U8, HG_I8, HG_U16, HG_I16, HG_I32, HG_I64, HG_F16, HG_BF16, HG_F32, HG_F64 = 
 HG_NEAREST, HG_LINEAR = 0, 1
 HG_OP_RECT_TO_HEX, HG_OP_HEX_TO_RECT, HG_OP_HEXRESIZE = 0, 1, 2
 HG_KERNEL_GENERAL, HG_KERNEL_NEAREST, HG_KERNEL_STREAM, HG_KERNEL_DOWN, HG_KERNEL_UP = range(5)
+HG_KERNEL_BACKWARD = 5          # hg_resample_plan(backward) only
 HG_PYR_FUSED, HG_PYR_FUSED_SHORT, HG_PYR_STREAM, HG_PYR_LDS = range(4)
 HG_CONV_BWD_GENERIC, HG_CONV_BWD_MFMA = 0, 1
 HG_CONV_FWD_OTHER, HG_CONV_FWD_MFMA_F32, HG_CONV_FWD_MFMA_BF16, HG_CONV_FWD_MFMA_BF16_DMA = range(4)
@@ -56,6 +57,8 @@ SIGNATURES = {
     "hg_resample_backward": ([_int, _vp, _vp, _int] + [_i64] * 5 + [_int, _vp], _int),
     "hg_lattice_maps": ([_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp], _int),
     "hg_resample_kernel": ([_int, _int, _int] + [_i64] * 5 + [_int], _int),
+    "hg_resample_plan": ([_int, _int, _int] + [_i64] * 5 + [_int, _int, _int,
+                                                            ctypes.POINTER(_int)], _int),
     "hg_hexconv2d_out_shape": ([_i64, _i64, _int, _int, _int, _int,
                                 ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _int),
     "hg_hexconv2d_generic_plan": ([_int] + [_i64] * 5 + [_int] * 6 + [ctypes.POINTER(_int)] * 4
@@ -146,6 +149,24 @@ def resample_kernel(op, src_dtype, dst_dtype, planes, h, w, h1, w1, interp=HG_LI
     if st < 0:
         check(st, "hg_resample_kernel")
     return st
+
+
+# enum hg_resample_plan_field, in order
+RESAMPLE_PLAN_FIELDS = ("kernel", "K", "window_cols", "band_rows", "pdp", "pc", "chunks", "units",
+                        "launched", "wave_per_unit", "DB", "P", "SEP", "nout", "lds")
+
+
+def resample_plan(op, src_dtype, dst_dtype, planes, h, w, h1, w1, interp=HG_LINEAR, src_align=0,
+                  backward=False):
+    """dict of RESAMPLE_PLAN_FIELDS: the kernel a resample call (backward: hg_resample_backward,
+    src_dtype its accumulator) would run and what it would be launched with, for a source whose
+    address has the low bits src_align (hg_resample_plan; nothing is launched).  The HYGRID_*
+    switches are read as the call reads them."""
+    out = (_int * len(RESAMPLE_PLAN_FIELDS))()
+    check(lib().hg_resample_plan(int(op), int(src_dtype), int(dst_dtype), int(planes), int(h),
+                                 int(w), int(h1), int(w1), int(interp), int(src_align),
+                                 int(bool(backward)), out), "hg_resample_plan")
+    return dict(zip(RESAMPLE_PLAN_FIELDS, out))
 
 
 def pyramid_level_kernel(x_dtype, y_dtype, batch, channels, h, w, h1, w1, even_odd_offset=0,

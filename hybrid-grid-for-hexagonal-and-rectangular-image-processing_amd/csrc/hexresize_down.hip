@@ -306,14 +306,15 @@ __global__ __launch_bounds__(HD_THREADS, HD_WPE) void k_hexresize_down(const Tin
 #ifndef HD_CPP
 #define HD_CPP 48           // planes per unit in the one-wave-per-unit grid (round 5)
 #endif
-template <typename Tin, typename Tout, int K, int DB, int P, bool SEP>
-static int hd_launch(const void* src, void* dst, HexDownGeom& D, hipStream_t st) {
+// Chunks and grid of a launch (hd_launch and the plan query: one copy): fills D.pc, D.nchunk and
+// D.units, returns the waves launched; *grid_out: the grid has one wave per unit.  PDP: the
+// kernel's planes in flight (TsCfg<DB>::PDP).
+static int64_t hd_chunks(HexDownGeom& D, int PDP, bool* grid_out) {
     // resident waves: 256 CUs x 4 SIMDs x 4 waves; units split into plane chunks until
     // there are >= upw units per resident wave (the records are then recomputed per chunk:
     // fewer, longer units amortise them, more units balance the waves; A/B switch
     // HYGRID_TSK_UPW, default 1)
     constexpr int64_t RESIDENT = 256 * 4 * 4;
-    constexpr int PDP = TsCfg<DB>::PDP;
     const char* ue = getenv("HYGRID_TSK_UPW");
     const int64_t upw = ue ? std::max(1, atoi(ue)) : 1;
     const int64_t tiles = (int64_t)D.nwin * D.nband;
@@ -337,6 +338,14 @@ static int hd_launch(const void* src, void* dst, HexDownGeom& D, hipStream_t st)
     D.units = tiles * D.nchunk;
     int64_t waves = std::min<int64_t>(D.units, RESIDENT);
     if (grid) waves = std::min<int64_t>(D.units, (int64_t)1 << 30);   // a wave per unit
+    *grid_out = grid;
+    return waves;
+}
+
+template <typename Tin, typename Tout, int K, int DB, int P, bool SEP>
+static int hd_launch(const void* src, void* dst, HexDownGeom& D, hipStream_t st) {
+    bool grid;
+    const int64_t waves = hd_chunks(D, TsCfg<DB>::PDP, &grid);
     const unsigned blocks = (unsigned)((waves + 3) / 4);
     hipLaunchKernelGGL((k_hexresize_down<Tin, Tout, K, DB, P, SEP>), dim3(blocks), dim3(HD_THREADS), 0, st,
                        (const Tin*)src, (Tout*)dst, D);
@@ -344,10 +353,10 @@ static int hd_launch(const void* src, void* dst, HexDownGeom& D, hipStream_t st)
 }
 
 // A triangle-blend resample (op: HG_OP_HEXRESIZE or HG_OP_HEX_TO_RECT, linear) on the
-// streaming kernel, or HG_EUNSUP (the caller runs k_resample_lds).  dry: check only (HG_OK if
-// the kernel would run).
+// streaming kernel, or HG_EUNSUP (the caller runs k_resample_lds).  plan: check and fill the
+// launch plan only (HG_OK if the kernel would run; stream.h).
 int tristream_try(int op, const void* src, void* dst, int sdt, int ddt, int64_t planes, int64_t h,
-                  int64_t w, int64_t h1, int64_t w1, hipStream_t st, bool dry) {
+                  int64_t w, int64_t h1, int64_t w1, hipStream_t st, ResamplePlan* plan) {
     if (env_is("HYGRID_DOWN", "0")) return HG_EUNSUP;   // A/B switch: general kernels only
     if (op != HG_OP_HEXRESIZE && op != HG_OP_HEX_TO_RECT) return HG_EUNSUP;
     if (sdt != HG_F16 && sdt != HG_BF16) return HG_EUNSUP;
@@ -396,7 +405,17 @@ int tristream_try(int op, const void* src, void* dst, int sdt, int ddt, int64_t 
     D.nout = nout;
     D.nwin = (int)((w1 + nout - 1) / nout);
     D.nband = (int)((h1 + RB - 1) / RB);
-    if (dry) return HG_OK;
+    if (plan) {
+        const int pdp = DB == 16 ? TsCfg<16>::PDP : TsCfg<4>::PDP;
+        bool grid;
+        plan->launched = hd_chunks(D, pdp, &grid);
+        plan->kernel = HG_KERNEL_DOWN;
+        plan->k = K; plan->window_cols = nout; plan->band_rows = RB; plan->pdp = pdp;
+        plan->pc = D.pc; plan->chunks = D.nchunk; plan->units = D.units;
+        plan->wave_per_unit = grid;
+        plan->db = DB; plan->p = P; plan->sep = sep; plan->nout = nout;
+        return HG_OK;
+    }
 #define HG_TSK2(TI, TO, S)                                                                     \
     if (DB == 4) return K == 4 ? hd_launch<TI, TO, 4, 4, HD_P4, S>(src, dst, D, st)            \
                                : hd_launch<TI, TO, HD_P4, 4, HD_P4, S>(src, dst, D, st);       \

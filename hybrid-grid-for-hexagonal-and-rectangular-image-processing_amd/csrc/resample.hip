@@ -416,7 +416,9 @@ static int check_sizes(int64_t planes, int64_t h, int64_t w, int64_t h1, int64_t
     return HG_OK;
 }
 
-static LaunchGeom plan(const Geom& g, int64_t planes) {
+// Tiles and plane chunks of the general kernels (launch_linear, launch_nearest and through them
+// the plan query: one copy).
+static LaunchGeom plan_chunks(const Geom& g, int64_t planes) {
     LaunchGeom L;
     L.g = g;
     L.planes = planes;
@@ -434,26 +436,52 @@ static LaunchGeom plan(const Geom& g, int64_t planes) {
     return L;
 }
 
-template <int OP, typename Tin, typename Tout, typename A>
-static int launch_linear(const void* src, void* dst, int64_t planes, const Geom& g,
-                         hipStream_t st) {
-    if (planes == 0 || g.h1 == 0 || g.w1 == 0) return HG_OK;
-    LaunchGeom L = plan(g, planes);
-    constexpr int V = VecOf<Tin>::N;
+// grid: x = tiles, y = chunks of L.pc planes
+static dim3 plan_grid(const LaunchGeom& L) {
+    const int64_t nty = (L.g.h1 + RS_TR - 1) / RS_TR;
+    return dim3((unsigned)(L.ntx * nty), (unsigned)((L.planes + L.pc - 1) / L.pc));
+}
+
+// LDS staging of a linear launch for input elements of esz bytes (V = 16 / esz per chunk), an
+// accumulator of asz bytes and a source at address `base`: sets L.vec_ok and, when the worst
+// tile's footprint fits (true: k_resample_lds, else k_resample_direct), L.cap.
+static bool plan_staging(LaunchGeom& L, int esz, int asz, uintptr_t base) {
+    const Geom& g = L.g;
+    const int V = 16 / esz;
     // LDS footprint bound of a 16x128 tile (rows (TR-1)*di + 2 + slack, cols
     // (TC-1)*dj + tap spread + chunk alignment on both ends)
     const double di = std::fabs(g.xs.step), dj = std::fabs(g.ys.step);
     const double rows = std::floor((RS_TR - 1) * di) + 4.0;
     const double cols = std::floor((RS_TC - 1) * dj) + 6.0 + 2.0 * V;
     const double cap = rows * cols;
-    const bool use_lds = cap * sizeof(A) + 16 <= RS_LDS_MAX &&
+    const bool use_lds = cap * asz + 16 <= RS_LDS_MAX &&
                          rows * std::ceil(cols / V) <= RS_MAXPF * RS_THREADS;
-    const uintptr_t base = reinterpret_cast<uintptr_t>(src);
-    L.vec_ok = (base % 16 == 0) && ((g.w * (int64_t)sizeof(Tin)) % 16 == 0) ? 1 : 0;
-    const int64_t nty = (g.h1 + RS_TR - 1) / RS_TR;
-    dim3 grid((unsigned)(L.ntx * nty), (unsigned)((planes + L.pc - 1) / L.pc));
+    L.vec_ok = (base % 16 == 0) && ((g.w * (int64_t)esz) % 16 == 0) ? 1 : 0;
+    if (use_lds) L.cap = (int)cap;
+    return use_lds;
+}
+
+static int plan_general(ResamplePlan* plan, int kernel, const LaunchGeom& L, int lds) {
+    const dim3 grid = plan_grid(L);
+    plan->kernel = kernel;
+    plan->k = 1; plan->window_cols = RS_TC; plan->band_rows = RS_TR;
+    plan->pc = L.pc; plan->chunks = grid.y;
+    plan->units = plan->launched = (int64_t)grid.x * grid.y;
+    plan->wave_per_unit = 1; plan->lds = lds;
+    return HG_OK;
+}
+
+template <int OP, typename Tin, typename Tout, typename A>
+static int launch_linear(const void* src, void* dst, int64_t planes, const Geom& g,
+                         hipStream_t st, ResamplePlan* plan) {
+    if (plan) plan->kernel = HG_KERNEL_GENERAL;
+    if (planes == 0 || g.h1 == 0 || g.w1 == 0) return HG_OK;
+    LaunchGeom L = plan_chunks(g, planes);
+    const bool use_lds = plan_staging(L, (int)sizeof(Tin), (int)sizeof(A),
+                                      reinterpret_cast<uintptr_t>(src));
+    if (plan) return plan_general(plan, HG_KERNEL_GENERAL, L, use_lds);
+    const dim3 grid = plan_grid(L);
     if (use_lds) {
-        L.cap = (int)cap;
         const size_t shmem = 16 + (size_t)L.cap * sizeof(A);
         hipLaunchKernelGGL((k_resample_lds<OP, Tin, Tout, A>), grid, dim3(RS_THREADS), shmem, st,
                            (const Tin*)src, (Tout*)dst, L);
@@ -466,14 +494,65 @@ static int launch_linear(const void* src, void* dst, int64_t planes, const Geom&
 
 template <int OP, typename E>
 static int launch_nearest(const void* src, void* dst, int64_t planes, const Geom& g,
-                          hipStream_t st) {
+                          hipStream_t st, ResamplePlan* plan) {
+    if (plan) plan->kernel = HG_KERNEL_NEAREST;
     if (planes == 0 || g.h1 == 0 || g.w1 == 0) return HG_OK;
-    LaunchGeom L = plan(g, planes);
-    const int64_t nty = (g.h1 + RS_TR - 1) / RS_TR;
-    dim3 grid((unsigned)(L.ntx * nty), (unsigned)((planes + L.pc - 1) / L.pc));
+    LaunchGeom L = plan_chunks(g, planes);
+    if (plan) return plan_general(plan, HG_KERNEL_NEAREST, L, -1);
+    const dim3 grid = plan_grid(L);
     hipLaunchKernelGGL((k_resample_nearest<OP, E>), grid, dim3(RS_THREADS), 0, st,
                        (const E*)src, (E*)dst, L);
     return launch_status();
+}
+
+// The dispatch of hg_rect_to_hex / hg_hex_to_rect / hg_hexresize, the only copy: the kernels in
+// the order they are tried.  plan == null: the first kernel whose domain holds the call runs.
+// Otherwise nothing is launched, src and dst are not dereferenced (src stands for its low
+// address bits) and *plan gets that kernel and its launch plan.
+template <int OP>
+static int resample_route(const void* src, void* dst, int sdt, int ddt, int64_t planes, int64_t h,
+                          int64_t w, int64_t h1, int64_t w1, int interp, hipStream_t s,
+                          ResamplePlan* plan) {
+    const Geom g = geom_for(OP, h, w, h1, w1);
+    if (OP == OP_R2H && (interp == HG_NEAREST || (interp == HG_LINEAR && !acc_is_double(sdt, ddt)))) {
+        // ~2x downsampling lattices (ConvertToHexagon, the demo): row-streaming kernel
+        const int rc = down_try(src, dst, sdt, ddt, planes, h, w, h1, w1, interp, s, plan);
+        if (rc != HG_EUNSUP) return rc;
+    }
+    if (OP != OP_R2H && interp == HG_NEAREST) {   // upsampling lattices (ConvertToHexagon^-1)
+        const int rc = triup_try(OP, src, dst, sdt, ddt, planes, h, w, h1, w1, interp, s, plan);
+        if (rc != HG_EUNSUP) return rc;
+    }
+    if (interp == HG_NEAREST) {
+        if (sdt != ddt) return HG_EDTYPE;
+        switch (dtype_size(sdt)) {
+        case 1: return launch_nearest<OP, uint8_t>(src, dst, planes, g, s, plan);
+        case 2: return launch_nearest<OP, uint16_t>(src, dst, planes, g, s, plan);
+        case 4: return launch_nearest<OP, uint32_t>(src, dst, planes, g, s, plan);
+        case 8: return launch_nearest<OP, uint64_t>(src, dst, planes, g, s, plan);
+        default: return HG_EDTYPE;
+        }
+    }
+    if (interp != HG_LINEAR) return HG_EINVAL;
+    if (!dtype_is_float(ddt)) return HG_EDTYPE;
+    const bool dbl = acc_is_double(sdt, ddt);
+    if (!dbl && OP != OP_RESIZE) {   // near-identity lattices: row-streaming kernels
+        const int rc = stream_try(OP, src, dst, sdt, ddt, planes, h, w, h1, w1, s, plan);
+        if (rc != HG_EUNSUP) return rc;
+    }
+    if (!dbl && OP != OP_R2H) {      // upsampling lattices: hex (h/2, w/2) -> rect (h, w)
+        const int rc = triup_try(OP, src, dst, sdt, ddt, planes, h, w, h1, w1, interp, s, plan);
+        if (rc != HG_EUNSUP) return rc;
+    }
+    if (!dbl && OP != OP_R2H) {      // ~2x hexresize (pyramid levels)
+        const int rc = tristream_try(OP, src, dst, sdt, ddt, planes, h, w, h1, w1, s, plan);
+        if (rc != HG_EUNSUP) return rc;
+    }
+    HG_DISPATCH_IN(sdt, TIN, HG_DISPATCH_FLOAT_OUT(ddt, TOUT, {
+        if (dbl) return launch_linear<OP, TIN, TOUT, double>(src, dst, planes, g, s, plan);
+        return launch_linear<OP, TIN, TOUT, float>(src, dst, planes, g, s, plan);
+    }));
+    return HG_EDTYPE;
 }
 
 template <int OP>
@@ -482,47 +561,27 @@ static int resample(const void* src, void* dst, int sdt, int ddt, int64_t planes
     int st = check_sizes(planes, h, w, h1, w1);
     if (st) return st;
     if (planes * h1 * w1 > 0 && (!dst || (h * w > 0 && !src))) return HG_EINVAL;
-    const Geom g = geom_for(OP, h, w, h1, w1);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (OP == OP_R2H && (interp == HG_NEAREST || (interp == HG_LINEAR && !acc_is_double(sdt, ddt)))) {
-        // ~2x downsampling lattices (ConvertToHexagon, the demo): row-streaming kernel
-        const int rc = down_try(src, dst, sdt, ddt, planes, h, w, h1, w1, interp, s);
-        if (rc != HG_EUNSUP) return rc;
+    return resample_route<OP>(src, dst, sdt, ddt, planes, h, w, h1, w1, interp,
+                              reinterpret_cast<hipStream_t>(stream), nullptr);
+}
+
+// resample_route without a launch, for a source whose address has the low bits `align`
+static int resample_query(int op, int sdt, int ddt, int64_t planes, int64_t h, int64_t w,
+                          int64_t h1, int64_t w1, int interp, int align, ResamplePlan* plan) {
+    int st = check_sizes(planes, h, w, h1, w1);
+    if (st) return st;
+    if (align < 0 || align > 255) return HG_EINVAL;
+    const void* src = reinterpret_cast<const void*>((uintptr_t)align);   // never dereferenced
+    switch (op) {
+    case HG_OP_RECT_TO_HEX:
+        return resample_route<OP_R2H>(src, nullptr, sdt, ddt, planes, h, w, h1, w1, interp, nullptr, plan);
+    case HG_OP_HEX_TO_RECT:
+        return resample_route<OP_H2R>(src, nullptr, sdt, ddt, planes, h, w, h1, w1, interp, nullptr, plan);
+    case HG_OP_HEXRESIZE:
+        return resample_route<OP_RESIZE>(src, nullptr, sdt, ddt, planes, h, w, h1, w1, interp, nullptr, plan);
+    default:
+        return HG_EINVAL;
     }
-    if (OP != OP_R2H && interp == HG_NEAREST) {   // upsampling lattices (ConvertToHexagon^-1)
-        const int rc = triup_try(OP, src, dst, sdt, ddt, planes, h, w, h1, w1, interp, s, false);
-        if (rc != HG_EUNSUP) return rc;
-    }
-    if (interp == HG_NEAREST) {
-        if (sdt != ddt) return HG_EDTYPE;
-        switch (dtype_size(sdt)) {
-        case 1: return launch_nearest<OP, uint8_t>(src, dst, planes, g, s);
-        case 2: return launch_nearest<OP, uint16_t>(src, dst, planes, g, s);
-        case 4: return launch_nearest<OP, uint32_t>(src, dst, planes, g, s);
-        case 8: return launch_nearest<OP, uint64_t>(src, dst, planes, g, s);
-        default: return HG_EDTYPE;
-        }
-    }
-    if (interp != HG_LINEAR) return HG_EINVAL;
-    if (!dtype_is_float(ddt)) return HG_EDTYPE;
-    const bool dbl = acc_is_double(sdt, ddt);
-    if (!dbl && OP != OP_RESIZE) {   // near-identity lattices: row-streaming kernels
-        const int rc = stream_try(OP, src, dst, sdt, ddt, planes, h, w, h1, w1, s);
-        if (rc != HG_EUNSUP) return rc;
-    }
-    if (!dbl && OP != OP_R2H) {      // upsampling lattices: hex (h/2, w/2) -> rect (h, w)
-        const int rc = triup_try(OP, src, dst, sdt, ddt, planes, h, w, h1, w1, interp, s, false);
-        if (rc != HG_EUNSUP) return rc;
-    }
-    if (!dbl && OP != OP_R2H) {      // ~2x hexresize (pyramid levels)
-        const int rc = tristream_try(OP, src, dst, sdt, ddt, planes, h, w, h1, w1, s, false);
-        if (rc != HG_EUNSUP) return rc;
-    }
-    HG_DISPATCH_IN(sdt, TIN, HG_DISPATCH_FLOAT_OUT(ddt, TOUT, {
-        if (dbl) return launch_linear<OP, TIN, TOUT, double>(src, dst, planes, g, s);
-        return launch_linear<OP, TIN, TOUT, float>(src, dst, planes, g, s);
-    }));
-    return HG_EDTYPE;
 }
 
 }  // namespace hg
@@ -547,33 +606,36 @@ int hg_hexresize(const void* src, void* dst, int sdt, int ddt, int64_t planes, i
 
 int hg_resample_kernel(int op, int sdt, int ddt, int64_t planes, int64_t h, int64_t w,
                        int64_t h1, int64_t w1, int interp) {
-    // the dispatch of hg::resample, without launching
-    int st = hg::check_sizes(planes, h, w, h1, w1);
-    if (st) return st;
-    if (op != HG_OP_RECT_TO_HEX && op != HG_OP_HEX_TO_RECT && op != HG_OP_HEXRESIZE) return HG_EINVAL;
-    if (interp == HG_NEAREST && sdt != ddt) return HG_EDTYPE;
-    if (interp != HG_NEAREST && interp != HG_LINEAR) return HG_EINVAL;
-    // resample() returns HG_EDTYPE for a non-float linear output (no kernel takes one: the
-    // down kernel's dtype checks decline it first)
-    if (interp == HG_LINEAR && !hg::dtype_is_float(ddt)) return HG_EDTYPE;
-    const bool dbl = interp == HG_LINEAR && hg::acc_is_double(sdt, ddt);
-    if (op == HG_OP_RECT_TO_HEX && !dbl &&
-        hg::down_try(nullptr, nullptr, sdt, ddt, planes, h, w, h1, w1, interp, nullptr, true) == HG_OK)
-        return HG_KERNEL_DOWN;
-    if (interp == HG_NEAREST && op != HG_OP_RECT_TO_HEX &&
-        hg::triup_try(op, nullptr, nullptr, sdt, ddt, planes, h, w, h1, w1, interp, nullptr, true) == HG_OK)
-        return HG_KERNEL_UP;
-    if (interp == HG_NEAREST) return HG_KERNEL_NEAREST;
-    if (!dbl && op != HG_OP_HEXRESIZE &&
-        hg::stream_try(op, nullptr, nullptr, sdt, ddt, planes, h, w, h1, w1, nullptr, true) == HG_OK)
-        return HG_KERNEL_STREAM;
-    if (!dbl && op != HG_OP_RECT_TO_HEX &&
-        hg::triup_try(op, nullptr, nullptr, sdt, ddt, planes, h, w, h1, w1, interp, nullptr, true) == HG_OK)
-        return HG_KERNEL_UP;
-    if (!dbl && op != HG_OP_RECT_TO_HEX && interp == HG_LINEAR &&
-        hg::tristream_try(op, nullptr, nullptr, sdt, ddt, planes, h, w, h1, w1, nullptr, true) == HG_OK)
-        return HG_KERNEL_DOWN;
-    return HG_KERNEL_GENERAL;
+    // the dispatch of hg::resample (resample_route), without launching
+    hg::ResamplePlan P;
+    const int st = hg::resample_query(op, sdt, ddt, planes, h, w, h1, w1, interp, 0, &P);
+    return st ? st : P.kernel;
+}
+
+int hg_resample_plan(int op, int sdt, int ddt, int64_t planes, int64_t h, int64_t w, int64_t h1,
+                     int64_t w1, int interp, int src_align, int backward, hg_host_int_out plan) {
+    if (!plan) return HG_EINVAL;
+    hg::ResamplePlan P;
+    if (backward) {   // hg_resample_backward's checks (src_dtype: its acc_dtype)
+        if (op < HG_OP_RECT_TO_HEX || op > HG_OP_HEXRESIZE) return HG_EINVAL;
+        if (interp != HG_NEAREST && interp != HG_LINEAR) return HG_EINVAL;
+        if (planes < 0 || h < 1 || w < 1 || h1 < 0 || w1 < 0) return HG_EINVAL;
+        if (sdt != HG_F32 && sdt != HG_F64) return HG_EDTYPE;
+        P.kernel = HG_KERNEL_BACKWARD;
+        if (planes > 0 && h1 * w1 > 0) hg::resample_bwd_plan(planes, h1, w1, &P);
+    } else {
+        const int st = hg::resample_query(op, sdt, ddt, planes, h, w, h1, w1, interp, src_align, &P);
+        if (st) return st;
+    }
+    auto i32 = [](int64_t v) { return (int)std::min<int64_t>(v, INT_MAX); };
+    plan[HG_RP_KERNEL] = P.kernel; plan[HG_RP_K] = P.k;
+    plan[HG_RP_WINDOW_COLS] = P.window_cols; plan[HG_RP_BAND_ROWS] = P.band_rows;
+    plan[HG_RP_PDP] = P.pdp; plan[HG_RP_PC] = P.pc;
+    plan[HG_RP_CHUNKS] = i32(P.chunks); plan[HG_RP_UNITS] = i32(P.units);
+    plan[HG_RP_LAUNCHED] = i32(P.launched); plan[HG_RP_WAVE_PER_UNIT] = P.wave_per_unit;
+    plan[HG_RP_DB] = P.db; plan[HG_RP_P] = P.p; plan[HG_RP_SEP] = P.sep;
+    plan[HG_RP_NOUT] = P.nout; plan[HG_RP_LDS] = P.lds;
+    return HG_OK;
 }
 
 int hg_lattice_maps(int op, int64_t h, int64_t w, int64_t h1, int64_t w1, int32_t* imaps,

@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "lattice.h"
+#include "stream.h"
 
 namespace hg {
 
@@ -81,19 +82,38 @@ __global__ __launch_bounds__(RB_THREADS) void k_resample_bwd(const A* __restrict
     }
 }
 
+// grid of a launch (resample_bwd_launch and the plan query: one copy): *bx blocks of 256 output
+// samples x *by chunks of *pc planes
+static void bwd_grid(int64_t planes, int64_t n_out, int64_t* bx, int64_t* by, int* pc) {
+    *bx = (n_out + RB_THREADS - 1) / RB_THREADS;
+    // enough workgroups to fill the chip; each reuses its lattice for pc planes
+    int64_t chunks = std::max<int64_t>(1, std::min<int64_t>(planes, (4096 + *bx - 1) / *bx));
+    chunks = std::min<int64_t>(chunks, 65535);
+    *pc = (int)((planes + chunks - 1) / chunks);
+    *by = (planes + *pc - 1) / *pc;
+}
+
+void resample_bwd_plan(int64_t planes, int64_t h1, int64_t w1, ResamplePlan* plan) {
+    int64_t bx, by;
+    int pc;
+    bwd_grid(planes, h1 * w1, &bx, &by, &pc);
+    plan->kernel = HG_KERNEL_BACKWARD;
+    plan->k = 1; plan->window_cols = RB_THREADS; plan->band_rows = 1;
+    plan->pc = pc; plan->chunks = by; plan->units = bx * by; plan->launched = bx * by;
+    plan->wave_per_unit = 1;
+}
+
 template <int OP, typename A>
 static int resample_bwd_launch(const void* gy, void* dx, const Geom& g, int64_t planes,
                                int interp, hipStream_t st) {
     const hipError_t e = hipMemsetAsync(dx, 0, sizeof(A) * (size_t)(planes * g.h * g.w), st);
     if (e != hipSuccess) return hip_status(e);
     const int64_t n_out = g.h1 * g.w1;
-    const int64_t bx = (n_out + RB_THREADS - 1) / RB_THREADS;
+    int64_t bx, by;
+    int pc;
+    bwd_grid(planes, n_out, &bx, &by, &pc);
     if (bx > INT_MAX) return HG_ESHAPE;
-    // enough workgroups to fill the chip; each reuses its lattice for pc planes
-    int64_t chunks = std::max<int64_t>(1, std::min<int64_t>(planes, (4096 + bx - 1) / bx));
-    chunks = std::min<int64_t>(chunks, 65535);
-    const int pc = (int)((planes + chunks - 1) / chunks);
-    const dim3 grid((unsigned)bx, (unsigned)((planes + pc - 1) / pc));
+    const dim3 grid((unsigned)bx, (unsigned)by);
     hipLaunchKernelGGL((k_resample_bwd<OP, A>), grid, dim3(RB_THREADS), 0, st, (const A*)gy,
                        (A*)dx, g, planes, interp, pc);
     return launch_status();

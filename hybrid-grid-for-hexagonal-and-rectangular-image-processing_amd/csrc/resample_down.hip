@@ -296,9 +296,14 @@ static bool down_lattice_ok(const Geom& g, int E, bool near) {
     return true;
 }
 
+// workgroups of a launch: one per (plane, band, group of 4 windows) (down_launch and the plan)
+static int64_t down_blocks(const DownGeom& D) {
+    return D.planes * (int64_t)D.nband * ((D.nwin + 3) / 4);
+}
+
 template <typename Tin, typename Tout, bool NEAR>
 static int down_launch(const void* src, void* dst, const DownGeom& D, hipStream_t st) {
-    const int64_t blocks = D.planes * (int64_t)D.nband * ((D.nwin + 3) / 4);
+    const int64_t blocks = down_blocks(D);
     if (blocks > INT_MAX) return HG_ESHAPE;
     hipLaunchKernelGGL((k_r2h_down<Tin, Tout, NEAR>), dim3((unsigned)blocks), dim3(DN_THREADS), 0,
                        st, (const Tin*)src, (Tout*)dst, D);
@@ -306,7 +311,7 @@ static int down_launch(const void* src, void* dst, const DownGeom& D, hipStream_
 }
 
 int down_try(const void* src, void* dst, int sdt, int ddt, int64_t planes, int64_t h, int64_t w,
-             int64_t h1, int64_t w1, int interp, hipStream_t st, bool dry) {
+             int64_t h1, int64_t w1, int interp, hipStream_t st, ResamplePlan* plan) {
     if (env_is("HYGRID_DOWN", "0")) return HG_EUNSUP;   // A/B switch: general kernels only
     const bool near = interp == HG_NEAREST;
     int E;
@@ -338,7 +343,14 @@ int down_try(const void* src, void* dst, int sdt, int ddt, int64_t planes, int64
     D.ys = g.ys;
     D.nwin = (int)((w1 + 64 * K - 1) / (64 * K));
     D.nband = (int)((h1 + DN_RB - 1) / DN_RB);
-    if (dry) return HG_OK;
+    if (plan) {   // one wave per (plane, band, window); a launch over INT_MAX blocks is HG_ESHAPE
+        plan->kernel = HG_KERNEL_DOWN;
+        plan->k = K; plan->window_cols = 64 * K; plan->band_rows = DN_RB; plan->pdp = DN_PD;
+        plan->pc = 1; plan->chunks = planes;
+        plan->units = planes * (int64_t)D.nband * D.nwin;
+        plan->launched = down_blocks(D); plan->wave_per_unit = 1;
+        return down_blocks(D) > INT_MAX ? HG_ESHAPE : HG_OK;
+    }
     if (near) {
         if (E == 1) return down_launch<uint8_t, uint8_t, true>(src, dst, D, st);
         return down_launch<uint16_t, uint16_t, true>(src, dst, D, st);

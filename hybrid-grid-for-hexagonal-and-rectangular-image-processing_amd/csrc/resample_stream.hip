@@ -434,9 +434,14 @@ __global__ __launch_bounds__(ST_THREADS) void k_h2r_stream(const Tin* __restrict
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
+// workgroups of a launch: one per (plane, band, group of 4 windows) (stream_launch and the plan)
+static int64_t stream_blocks(const StreamGeom& S) {
+    return S.planes * (int64_t)S.nband * ((S.nwin + 3) / 4);
+}
+
 template <typename Tin, typename Tout>
 static int stream_launch(int op, const void* src, void* dst, const StreamGeom& S, hipStream_t st) {
-    const int64_t blocks = S.planes * (int64_t)S.nband * ((S.nwin + 3) / 4);
+    const int64_t blocks = stream_blocks(S);
     if (blocks > INT_MAX) return HG_EUNSUP;
     if (blocks == 0) return HG_OK;
     if (op == HG_OP_RECT_TO_HEX)
@@ -493,7 +498,7 @@ static bool h2r_exact(const Geom& g, float tri[2][3]) {
 }
 
 int stream_try(int op, const void* src, void* dst, int sdt, int ddt, int64_t planes, int64_t h,
-               int64_t w, int64_t h1, int64_t w1, hipStream_t st, bool dry) {
+               int64_t w, int64_t h1, int64_t w1, hipStream_t st, ResamplePlan* plan) {
     if (env_is("HYGRID_STREAM", "0")) return HG_EUNSUP;   // A/B switch: general kernels only
     if (op != HG_OP_RECT_TO_HEX && op != HG_OP_HEX_TO_RECT) return HG_EUNSUP;
     auto small = [](int dt) { return dt == HG_BF16 || dt == HG_F16 || dt == HG_F32; };
@@ -517,7 +522,15 @@ int stream_try(int op, const void* src, void* dst, int sdt, int ddt, int64_t pla
     S.nwin = (int)((w1 + 64 * cpl - 1) / (64 * cpl));
     S.rb = op == HG_OP_RECT_TO_HEX ? ST_RB_R2H : ST_RB_H2R;
     S.nband = (int)((h1 + S.rb - 1) / S.rb);
-    if (dry) return HG_OK;
+    if (plan) {   // one wave per (plane, band, window); a plane's waves share no records
+        if (stream_blocks(S) > INT_MAX) return HG_EUNSUP;   // as stream_launch
+        plan->kernel = HG_KERNEL_STREAM;
+        plan->k = cpl; plan->window_cols = 64 * cpl; plan->band_rows = S.rb;
+        plan->pc = 1; plan->chunks = planes;
+        plan->units = planes * (int64_t)S.nband * S.nwin;
+        plan->launched = stream_blocks(S); plan->wave_per_unit = 1;
+        return HG_OK;
+    }
     if (sdt == HG_BF16 && ddt == HG_BF16) return stream_launch<__bf16, __bf16>(op, src, dst, S, st);
     if (sdt == HG_F16 && ddt == HG_F16) return stream_launch<_Float16, _Float16>(op, src, dst, S, st);
     if (sdt == HG_F32 && ddt == HG_F32) return stream_launch<float, float>(op, src, dst, S, st);

@@ -365,8 +365,10 @@ void k_tri_up(const Tin* __restrict__ x, Tout* __restrict__ y, TriUpGeom D) {
     }
 }
 
-template <typename Tin, typename Tout, int K, bool NEAR>
-static int tu_launch(const void* src, void* dst, TriUpGeom& D, hipStream_t st) {
+// Chunks and grid of a launch (tu_launch and the plan query: one copy): fills D.pc and D.units,
+// returns the waves launched; *grid_out: the grid has one wave per unit.  ein / eout: element
+// bytes in and out; pdp: the kernel's planes in flight (TuCfg<NEAR>::PDP).
+static int64_t tu_chunks(TriUpGeom& D, int ein, int eout, int pdp, bool* grid_out) {
     // units ~ the resident waves (256 CUs x 4 SIMDs x 4): plane chunks only when the tiles
     // alone leave most of them idle (the records are recomputed per chunk)
     // Round 5: a unit is (window, band, chunk of ~TU_CPP planes) and the grid has one wave per
@@ -389,15 +391,26 @@ static int tu_launch(const void* src, void* dst, TriUpGeom& D, hipStream_t st) {
         nchunk = std::max<int64_t>(1, std::min<int64_t>(D.planes, atoi(e)));
     // a chunk's planes are one buffer each way: 32-bit offsets, including the planes past the
     // chunk the prefetch addresses (out of range: zeros)
-    const int64_t plane_bytes = std::max<int64_t>((int64_t)D.h * D.w * (int64_t)sizeof(Tin),
-                                                  (int64_t)D.h1 * D.w1 * (int64_t)sizeof(Tout));
-    const int64_t max_pc = std::max<int64_t>(1, (((int64_t)1 << 31) - 1) / plane_bytes - TuCfg<NEAR>::PDP - 1);
+    const int64_t plane_bytes = std::max<int64_t>((int64_t)D.h * D.w * (int64_t)ein,
+                                                  (int64_t)D.h1 * D.w1 * (int64_t)eout);
+    const int64_t max_pc = std::max<int64_t>(1, (((int64_t)1 << 31) - 1) / plane_bytes - pdp - 1);
     nchunk = std::max<int64_t>(nchunk, (D.planes + max_pc - 1) / max_pc);
     D.pc = (int)((D.planes + nchunk - 1) / nchunk);
     nchunk = (D.planes + D.pc - 1) / D.pc;
     D.units = tiles * nchunk;
     int64_t waves = std::min<int64_t>(D.units, RESIDENT);
-    if (grid || env_is("HYGRID_TU_GRID", "1")) waves = std::min<int64_t>(D.units, (int64_t)1 << 30);
+    if (grid || env_is("HYGRID_TU_GRID", "1")) {
+        waves = std::min<int64_t>(D.units, (int64_t)1 << 30);
+        grid = true;
+    }
+    *grid_out = grid;
+    return waves;
+}
+
+template <typename Tin, typename Tout, int K, bool NEAR>
+static int tu_launch(const void* src, void* dst, TriUpGeom& D, hipStream_t st) {
+    bool grid;
+    const int64_t waves = tu_chunks(D, (int)sizeof(Tin), (int)sizeof(Tout), TuCfg<NEAR>::PDP, &grid);
     const unsigned blocks = (unsigned)((waves + 3) / 4);
     hipLaunchKernelGGL((k_tri_up<Tin, Tout, K, NEAR>), dim3(blocks), dim3(TU_THREADS), 0, st,
                        (const Tin*)src, (Tout*)dst, D);
@@ -406,9 +419,10 @@ static int tu_launch(const void* src, void* dst, TriUpGeom& D, hipStream_t st) {
 
 // An upsampling triangle resample (op HG_OP_HEX_TO_RECT or HG_OP_HEXRESIZE; 'linear' with
 // fp32 accumulation, 16/32-bit float in and out; 'nearest' on 8/16/32-bit elements) on the
-// streaming kernel, or HG_EUNSUP (the caller runs the general kernels).  dry: check only.
+// streaming kernel, or HG_EUNSUP (the caller runs the general kernels).  plan: check and fill
+// the launch plan only (stream.h).
 int triup_try(int op, const void* src, void* dst, int sdt, int ddt, int64_t planes, int64_t h,
-              int64_t w, int64_t h1, int64_t w1, int interp, hipStream_t st, bool dry) {
+              int64_t w, int64_t h1, int64_t w1, int interp, hipStream_t st, ResamplePlan* plan) {
     if (env_is("HYGRID_DOWN", "0") || env_is("HYGRID_UP", "0")) return HG_EUNSUP;   // A/B switches
     if (op != HG_OP_HEX_TO_RECT && op != HG_OP_HEXRESIZE) return HG_EUNSUP;
     const bool near_ = interp == HG_NEAREST;
@@ -452,7 +466,16 @@ int triup_try(int op, const void* src, void* dst, int sdt, int ddt, int64_t plan
     D.h = (int)h; D.w = (int)w; D.h1 = (int)h1; D.w1 = (int)w1;
     D.nwin = (int)((w1 + 64 * K - 1) / (64 * K));
     D.nband = (int)((h1 + RB - 1) / RB);
-    if (dry) return HG_OK;
+    if (plan) {
+        const int pdp = near_ ? TuCfg<true>::PDP : TuCfg<false>::PDP;
+        bool grid;
+        plan->launched = tu_chunks(D, E, EO, pdp, &grid);
+        plan->kernel = HG_KERNEL_UP;
+        plan->k = K; plan->window_cols = 64 * K; plan->band_rows = RB; plan->pdp = pdp;
+        plan->pc = D.pc; plan->chunks = D.units / ((int64_t)D.nwin * D.nband);
+        plan->units = D.units; plan->wave_per_unit = grid;
+        return HG_OK;
+    }
 #define HG_TU_K(TI, TO, KN, NR_)                                                                \
     return K == 1 ? tu_launch<TI, TO, 1, NR_>(src, dst, D, st) : tu_launch<TI, TO, KN, NR_>(src, dst, D, st);
     if (near_) {

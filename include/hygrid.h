@@ -121,9 +121,50 @@ int hg_resample_backward(int op, const void* gy, void* dx, int acc_dtype, int64_
  * takes the hexresize streaming kernel's 4-B-piece layout, whose narrower windows can decline
  * where the query said HG_KERNEL_DOWN: that call then runs the general kernel. */
 enum hg_kernel { HG_KERNEL_GENERAL = 0, HG_KERNEL_NEAREST = 1, HG_KERNEL_STREAM = 2,
-                 HG_KERNEL_DOWN = 3, HG_KERNEL_UP = 4 };
+                 HG_KERNEL_DOWN = 3, HG_KERNEL_UP = 4,
+                 HG_KERNEL_BACKWARD = 5 /* k_resample_bwd: hg_resample_plan(backward) only */ };
 int hg_resample_kernel(int op, int src_dtype, int dst_dtype, int64_t planes, int64_t h, int64_t w,
                        int64_t h1, int64_t w1, int interp);
+
+/* An answer slot of a host-only query: the address of an int (hg_resample_plan: of an array of
+ * ints) in HOST memory (an `int*`; pass `&k`).  Its own type, so that a declaration says the
+ * library never writes device memory through it: every plain non-const pointer in this header
+ * is a buffer a kernel may write. */
+typedef int* hg_host_int_out;
+
+/* The launch plan of a resample call (nothing is launched, no device is touched): the kernel
+ * hg_resample_kernel names and what it would be started with, computed by the host code the
+ * call itself runs (one routing function, one chunk computation per kernel), the HYGRID_*
+ * switches read as the call reads them.  src_align: the low bits (0..255) of the source
+ * address the answer is for; 0 answers for a 16-byte-aligned source as hg_resample_kernel does,
+ * 4 for a 4-B but not 16-B aligned one.  backward != 0: the plan of hg_resample_backward for
+ * this op and sizes instead, with src_dtype its acc_dtype (dst_dtype and src_align unused).
+ * plan: HG_RP_N ints in HOST memory, indexed by hg_resample_plan_field; a field that does not
+ * apply to the kernel is 0 (HG_RP_LDS: -1).  An empty call fills the kernel only.  Counts
+ * beyond INT_MAX saturate.  Returns the negative status the call would return.
+ * Introspection for tests, which file their cases by it; the reference has no counterpart. */
+enum hg_resample_plan_field {
+    HG_RP_KERNEL = 0,      /* hg_kernel */
+    HG_RP_K,               /* adjacent output columns per lane (general kernels: 1 per thread) */
+    HG_RP_WINDOW_COLS,     /* output columns of one unit's window (k_hexresize_down: nout) */
+    HG_RP_BAND_ROWS,       /* output rows of one unit's band */
+    HG_RP_PDP,             /* planes (k_r2h_down: rows) of input in flight ahead of the one computed */
+    HG_RP_PC,              /* planes one unit walks */
+    HG_RP_CHUNKS,          /* plane chunks: ceil(planes / pc) */
+    HG_RP_UNITS,           /* windows x bands x chunks (general kernels, backward: tiles x chunks) */
+    HG_RP_LAUNCHED,        /* k_tri_up, k_hexresize_down: waves (the grid is ceil(waves / 4)
+                              workgroups); every other kernel: workgroups */
+    HG_RP_WAVE_PER_UNIT,   /* 1: no wave or workgroup walks more than one unit */
+    HG_RP_DB,              /* k_hexresize_down: bytes of an input-row piece per lane (16 or 4) */
+    HG_RP_P,               /* k_hexresize_down: adjacent columns per store */
+    HG_RP_SEP,             /* k_hexresize_down: every output row loads its own two input rows */
+    HG_RP_NOUT,            /* k_hexresize_down: output columns per window */
+    HG_RP_LDS,             /* HG_KERNEL_GENERAL: 1 k_resample_lds, 0 k_resample_direct; else -1 */
+    HG_RP_N
+};
+int hg_resample_plan(int op, int src_dtype, int dst_dtype, int64_t planes, int64_t h, int64_t w,
+                     int64_t h1, int64_t w1, int interp, int src_align, int backward,
+                     hg_host_int_out plan);
 
 /* Integer lattice maps (and fp64 coefficients) of one resample, for parity tests.
  * imaps: int32 [5][h1][w1] = i_n, j_n, up_down_flag, valid bitmask (bit k-1 =
@@ -216,10 +257,6 @@ int hg_hexconv2d_backward(const void* x, const void* kernel, const void* gy, voi
  * selects load widths inside a kernel, never the kernel).  Returns the negative status
  * hg_hexconv2d_backward would return for bad arguments. */
 enum hg_conv_bwd_kernel { HG_CONV_BWD_GENERIC = 0, HG_CONV_BWD_MFMA = 1 };
-/* An answer slot of a host-only query: the address of an int in HOST memory (an `int*`; pass
- * `&k`).  Its own type, so that a declaration says the library never writes device memory
- * through it: every plain non-const pointer in this header is a buffer a kernel may write. */
-typedef int* hg_host_int_out;
 int hg_hexconv2d_backward_plan(int x_dtype, int w_dtype, int64_t batch, int64_t in_channels,
                                int64_t out_channels, int64_t h, int64_t w, int radius,
                                int stride, int padding, int dilation, int groups, int pad_mode,

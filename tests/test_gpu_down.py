@@ -9,6 +9,7 @@ it is asserted BIT-IDENTICAL to the general kernels (selected with HYGRID_DOWN=0
 every call), NaN/Inf included; nearest is also bit-exact against the fp64 oracle
 (oracle/hg_oracle.c, pinned to geometry_np.py:358-519 by tests/golden), bilinear within the
 north_star tolerance (rtol 1e-5 of max|ref| for fp32 outputs, one output rounding for 16-bit).
+Every comparison first asserts, through the host-only dispatch query, which kernel each side runs.
 """
 import os
 
@@ -28,18 +29,34 @@ from HyGrid import _abi, ops  # noqa: E402
 DEV = torch.device("cuda:0")
 
 
-def _general(fn, *args, **kw):
+def _down_off(fn, *args, **kw):
     old = os.environ.get("HYGRID_DOWN")
     os.environ["HYGRID_DOWN"] = "0"
     try:
         out = fn(*args, **kw)
-        torch.cuda.synchronize()
+        if isinstance(out, torch.Tensor):
+            torch.cuda.synchronize()
         return out
     finally:
         if old is None:
             del os.environ["HYGRID_DOWN"]
         else:
             os.environ["HYGRID_DOWN"] = old
+
+
+def _kernel(x, size, interp=_abi.HG_LINEAR, out_dtype=None):
+    """The kernel ops.rect_to_hex(x, size, ...) runs under the current switches."""
+    planes = x.numel() // (x.shape[-2] * x.shape[-1])
+    od = x.dtype if out_dtype is None or interp == _abi.HG_NEAREST else out_dtype
+    return _abi.resample_kernel(_abi.HG_OP_RECT_TO_HEX, _abi.dtype_code(x.dtype), _abi.dtype_code(od),
+                                planes, x.shape[-2], x.shape[-1], size[0], size[1], interp)
+
+
+def _general(fn, x, size, interp=_abi.HG_LINEAR, out_dtype=None):
+    """The call on the general kernels (asserted to be the ones that run)."""
+    want = _abi.HG_KERNEL_NEAREST if interp == _abi.HG_NEAREST else _abi.HG_KERNEL_GENERAL
+    assert _down_off(_kernel, x, size, interp, out_dtype) == want
+    return _down_off(fn, x, size, interp=interp, out_dtype=out_dtype)
 
 
 def _bits(t):
@@ -72,6 +89,10 @@ def test_convert_to_hexagon_nearest_u8(h, w):
     the general kernel and the oracle agree bit for bit."""
     x = _u8((2, 3, h, w), h * 7 + w)
     size = (h // 2, w // 2)
+    # 8-byte rows are narrower than the streaming kernel's 16-byte chunk: (4, 8) runs, and is
+    # compared with, k_resample_nearest; the oracle below is what checks it
+    want = _abi.HG_KERNEL_NEAREST if (h, w) == (4, 8) else _abi.HG_KERNEL_DOWN
+    assert _kernel(x, size, _abi.HG_NEAREST) == want
     y = ops.rect_to_hex(x, size, interp=_abi.HG_NEAREST)
     torch.cuda.synchronize()
     _same_bits(y, _general(ops.rect_to_hex, x, size, interp=_abi.HG_NEAREST))
@@ -86,6 +107,7 @@ def test_nearest_16bit(h, w, dt):
     g = torch.Generator(device=DEV).manual_seed(h + w)
     x = (torch.randn((2, h, w), generator=g, device=DEV) * 100).to(dt)
     size = (h // 2, w // 2)
+    assert _kernel(x, size, _abi.HG_NEAREST) == _abi.HG_KERNEL_DOWN
     y = ops.rect_to_hex(x, size, interp=_abi.HG_NEAREST)
     torch.cuda.synchronize()
     _same_bits(y, _general(ops.rect_to_hex, x, size, interp=_abi.HG_NEAREST))
@@ -102,6 +124,7 @@ def test_bilinear_2x(h, w, size, dt, out):
     tolerance of the fp64 oracle."""
     g = torch.Generator(device=DEV).manual_seed(h * 3 + w)
     x = torch.rand((2, 3, h, w), generator=g, device=DEV).to(dt)
+    assert _kernel(x, size, out_dtype=out) == _abi.HG_KERNEL_DOWN
     y = ops.rect_to_hex(x, size, out_dtype=out)
     torch.cuda.synchronize()
     _same_bits(y, _general(ops.rect_to_hex, x, size, out_dtype=out))
@@ -126,6 +149,7 @@ def test_nonfinite_bit_identical():
     x[0, 64, 259] = float("-inf")
     x[0, 129, 100] = float("nan")
     for interp in (_abi.HG_LINEAR, _abi.HG_NEAREST):
+        assert _kernel(x, (h // 2, w // 2), interp) == _abi.HG_KERNEL_DOWN
         y = ops.rect_to_hex(x, (h // 2, w // 2), interp=interp)
         torch.cuda.synchronize()
         _same_bits(y, _general(ops.rect_to_hex, x, (h // 2, w // 2), interp=interp))
