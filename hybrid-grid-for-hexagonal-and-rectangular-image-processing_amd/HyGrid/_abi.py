@@ -28,6 +28,7 @@ HG_OP_RECT_TO_HEX, HG_OP_HEX_TO_RECT, HG_OP_HEXRESIZE = 0, 1, 2
 HG_KERNEL_GENERAL, HG_KERNEL_NEAREST, HG_KERNEL_STREAM, HG_KERNEL_DOWN, HG_KERNEL_UP = range(5)
 HG_KERNEL_BACKWARD = 5          # hg_resample_plan(backward) only
 HG_PYR_FUSED, HG_PYR_FUSED_SHORT, HG_PYR_STREAM, HG_PYR_LDS = range(4)
+HG_POOL_SMALL, HG_POOL_LARGE = 0, 1
 HG_CONV_BWD_GENERIC, HG_CONV_BWD_MFMA = 0, 1
 HG_CONV_FWD_OTHER, HG_CONV_FWD_MFMA_F32, HG_CONV_FWD_MFMA_BF16, HG_CONV_FWD_MFMA_BF16_DMA = range(4)
 HG_OK, HG_EINVAL, HG_EDTYPE, HG_ESHAPE, HG_EUNSUP, HG_EOVERFLOW = 0, -1, -2, -3, -4, -5
@@ -83,6 +84,7 @@ SIGNATURES = {
     "hg_hex_pool2d_backward": ([_vp, _vp, _vp, _int, _int, _int] + [_i64] * 3
                                + [_int, _int, _dbl, _i64, _i64, _dbl] + [_int] * 4
                                + [_i64, _i64, _vp], _int),
+    "hg_hex_pool2d_route": ([_int, _int, _int], _int),
     "hg_hex_pyramid_level": ([_vp, _vp, _int, _int] + [_i64] * 6 + [_vp, _vp, _int, _int, _vp],
                              _int),
     "hg_hex_pyramid_level_kernel": ([_int, _int] + [_i64] * 6 + [_int, _int], _int),
@@ -177,6 +179,15 @@ def pyramid_level_kernel(x_dtype, y_dtype, batch, channels, h, w, h1, w1, even_o
                                            int(bool(from_rect)))
     if st < 0:
         check(st, "hg_hex_pyramid_level_kernel")
+    return st
+
+
+def hex_pool2d_route(kh, kw, backward=False):
+    """Which kernels hex pooling (backward: its gradient) runs for a kh x kw window:
+    HG_POOL_SMALL or HG_POOL_LARGE (hg_hex_pool2d_route; nothing is launched)."""
+    st = lib().hg_hex_pool2d_route(int(kh), int(kw), int(bool(backward)))
+    if st < 0:
+        check(st, "hg_hex_pool2d_route")
     return st
 
 

@@ -313,11 +313,18 @@ static int pool_setup(PoolGeom* g, int method, int64_t planes, int64_t h, int64_
     return HG_OK;
 }
 
+// The one routing decision of both directions (hg_hex_pool2d_route reports it): a window of
+// PL_LARGE elements and more gets a workgroup per output, a smaller one a thread per output.
+static int pool_route(int64_t kh, int64_t kw, bool backward) {
+    (void)backward;   // the backward recomputes the forward's reduction: one threshold for both
+    return kh * kw >= PL_LARGE ? HG_POOL_LARGE : HG_POOL_SMALL;
+}
+
 template <typename T>
 static int launch_pool(const void* x, void* y, const PoolGeom& g, hipStream_t s) {
     const int64_t nout = g.planes * g.hn * g.wn;
     if (nout == 0) return HG_OK;
-    if ((int64_t)g.kh * g.kw >= PL_LARGE) {
+    if (pool_route(g.kh, g.kw, false) == HG_POOL_LARGE) {
         hipLaunchKernelGGL(k_pool_large<T>, dim3((unsigned)nout), dim3(PL_THREADS), 0, s,
                            static_cast<const T*>(x), static_cast<T*>(y), g);
     } else {
@@ -332,7 +339,7 @@ static int launch_pool_bwd(const void* x, const void* gy, void* dx, const PoolGe
                            hipStream_t s) {
     const int64_t nout = g.planes * g.hn * g.wn;
     if (nout == 0) return HG_OK;
-    if ((int64_t)g.kh * g.kw >= PL_LARGE) {
+    if (pool_route(g.kh, g.kw, true) == HG_POOL_LARGE) {
         hipLaunchKernelGGL((k_pool_bwd_large<T, G>), dim3((unsigned)nout), dim3(PL_THREADS), 0, s,
                            static_cast<const T*>(x), static_cast<const G*>(gy),
                            static_cast<G*>(dx), g);
@@ -348,6 +355,11 @@ static int launch_pool_bwd(const void* x, const void* gy, void* dx, const PoolGe
 }  // namespace hg
 
 extern "C" {
+
+int hg_hex_pool2d_route(int kh, int kw, int backward) {
+    if (kh < 0 || kw < 0) return HG_EINVAL;
+    return hg::pool_route(kh, kw, backward != 0);
+}
 
 int hg_hex_pool2d(const void* x, void* y, int dtype, int method, int64_t planes, int64_t h,
                   int64_t w, int pad, int pad_mode, double pad_value, int64_t ext_h,

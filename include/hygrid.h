@@ -329,6 +329,14 @@ int hg_hex_pool2d_backward(const void* x, const void* gy, void* dx, int dtype, i
                            int pad_mode, double pad_value, int64_t ext_h, int64_t ext_w,
                            double ext_value, int kh, int kw, int sh, int sw, int64_t hn,
                            int64_t wn, void* stream);
+/* Which kernels hg_hex_pool2d (backward != 0: hg_hex_pool2d_backward) runs for a kh x kw
+ * window (nothing is launched, no device is touched): HG_POOL_SMALL, one thread per output
+ * (k_pool_small / k_pool_bwd_small), or HG_POOL_LARGE, one 256-thread workgroup per output
+ * with an LDS tree (k_pool_large / k_pool_bwd_large; windows of 512 elements and more), or
+ * HG_EINVAL for a negative size.  The host function that routes the real launches answers.
+ * Introspection for tests, which file their cases by it; the reference has no counterpart. */
+enum hg_pool_kernel { HG_POOL_SMALL = 0, HG_POOL_LARGE = 1 };
+int hg_hex_pool2d_route(int kh, int kw, int backward);
 int hg_hex_homography_maps(int64_t h, int64_t w, int64_t h1, int64_t w1, const double* xs,
                            const double* ys, const double* hinv, int32_t* imaps, double* fmaps,
                            void* stream);

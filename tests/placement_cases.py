@@ -622,6 +622,9 @@ pool("pool_large_global_average_f32", (2, 3, 24, 32), F32, dict(kind="global", m
      2e-6, 1e-5)
 pool("pool_large_adaptive_max_f16", (2, 3, 70, 99), F16, dict(kind="adaptive", method="max", outsize=2),
      None, 4e-3)
+# the large kernels behind HexPool2d: 23 x 23 windows whose reflect frame folds onto x
+pool("pool_large_min_reflect_ceil_f32", (2, 2, 50, 61), F32,
+     dict(kind="pool", method="min", k=23, s=23, pad=3, mode="reflect", ceil=True), None, 1e-5)
 
 
 # ---- pyramid: hg_hex_pyramid_level, hg_hex_pyramid_chain --------------------------------------

@@ -116,9 +116,26 @@ def test_global_and_adaptive_large(method):
     np.testing.assert_allclose(a.double().cpu().numpy(), aref, rtol=1e-6, atol=1e-7)
     xr = x.double().requires_grad_(True)
     HF.HexGlobalPool2d(method)(xr).sum().backward()
-    dref = O.hex_pool2d_backward(x.double().cpu().numpy(), np.ones((2, 3)), method,
-                                 540, 960, 540, 960, 1, 1)
+    gargs = (method, 540, 960, 540, 960, 1, 1)
+    dref = O.hex_pool2d_backward(x.double().cpu().numpy(), np.ones((2, 3)), *gargs)
     np.testing.assert_allclose(xr.grad.cpu().numpy(), dref, rtol=1e-14, atol=1e-15)
+    # k_pool_bwd_large beyond global fp64: the adaptive windows, and f32 / bf16 inputs with
+    # the fp32 gradient buffer (bounds: fp64 as above, the rest test_pool_random_vs_oracle's)
+    xr = x.double().requires_grad_(True)
+    HF.HexAdaptivePool2d(7, method)(xr).sum().backward()
+    daref = O.hex_pool2d_backward(x.double().cpu().numpy(), np.ones((2, 3, 7, 7)), *args)
+    np.testing.assert_allclose(xr.grad.cpu().numpy(), daref, rtol=1e-14, atol=1e-15)
+    for dtype, tol in ((torch.float32, 1e-5), (torch.bfloat16, 3e-2)):
+        xt = x.to(dtype)
+        xo = xt.double().cpu().numpy()
+        for mod, ones, a in ((HF.HexGlobalPool2d(method), np.ones((2, 3)), gargs),
+                             (HF.HexAdaptivePool2d(7, method), np.ones((2, 3, 7, 7)), args)):
+            xr = xt.clone().requires_grad_(True)
+            mod(xr).sum().backward()
+            assert xr.grad.dtype == dtype
+            d = dref if dtype == torch.float32 and a is gargs else \
+                daref if dtype == torch.float32 else O.hex_pool2d_backward(xo, ones, *a)
+            np.testing.assert_allclose(xr.grad.double().cpu().numpy(), d, rtol=tol, atol=tol)
 
 
 def test_reduce_functions():
