@@ -1,17 +1,26 @@
 // fused4.hip — the headline pass (rect -> hex -> HexConv2d(r=2) -> hex -> rect, bf16 in and out,
 // C = O = 3) with FOUR columns per lane (round 4): lane l owns columns ce .. ce + 3,
-// ce = W0 + 4 l, of a 256-column window (240 owned, 8 + 8 halo), as two (even, odd) pairs
-// A = (ce, ce + 1) and B = (ce + 2, ce + 3).  Everything else is k_fused MD 0 (fused_kernel.h):
+// ce = W0 + 4 l, of a 256-column window (240 owned, 8 + 8 halo), as two stride-2 pairs
+// P = (ce, ce + 2) and Q = (ce + 1, ce + 3) (round 8; rounds 4-7 held (even, odd) pairs
+// A = (ce, ce + 1), B = (ce + 2, ce + 3)).  Everything else is k_fused MD 0 (fused_kernel.h):
 // the per-wave row table and row classes, the per-lane column weights and column classes, the
 // packed 7-tap stencil with 21 weight pairs in SGPRs, the folded same-size h2r, the 6-step blocks.
 //
 // Why: per owned column the 2-column kernel spends a neighbour exchange (DPP + pair copies) on
 // every pair, 1/16 of its work on the 8-column window halo and reads 1.107x its input bytes;
-// here the neighbours of pair A are pair B's values (no DPP), the halo is 1/32 and the reads
+// here three of a lane's four columns have both neighbours in the lane, the halo is 1/32 and the reads
 // ~1.04x; 8-B loads and stores per lane (walk6: the access pattern alone 0.615 -> 0.657 of
 // 8 TB/s at 42-row bands, 0.73 at 18-24; profiles/r04/walk6_b.txt).  Registers: 29 of the 32
 // weight pairs in SGPRs (106 SGPRs) and two rect rows of prefetch: 136 VGPRs, 3 waves per SIMD
 // (round 6; one row of prefetch at 124 VGPRs and 4 waves was rounds 4-5's choice).
+//
+// Why stride-2 pairs: the kernel is bound by VALU issue, and with (even, odd)
+// pairs every odd tap shift needs a pair that straddles A and B, copied together by plain and
+// DPP moves (13 + 12 per step).  With P and Q, shift 0 reads (P, Q), +1 reads (Q, (P.y, next
+// lane's P.x)), -1 reads ((previous lane's Q.y, Q.x), P): two assembled pairs per channel, and
+// half of the horizontal blend and of the h2r become packed ops on aligned pairs.  Every
+// product and sum keeps its operands and order.  128-130 VGPRs; 196 VALU issue slots per step
+// in the two-term loops instead of 216-220 (profiles/r08/fused4_loop_mix.txt).
 //
 // Domain: fused_try's (same-size lattice, padding 1, value 0) with bf16 in and out, C = O = 3,
 // groups 1, w and w2 multiples of 4.  (Round 5 also built this layout for HexConv2d alone and
@@ -42,7 +51,9 @@ namespace hg {
 #define F4_ORDER 0                     // workgroup order (A/B): 0 group fastest, 1 band fastest
 #endif
 #ifndef F4_WPE
-#define F4_WPE 3                       // waves per SIMD asked of the register allocator
+#define F4_WPE 3                       // waves per SIMD, both the least and the most: at 128
+                                       // VGPRs the bench's instantiation would run 4, which
+                                       // is no faster (profiles/r08/fused4_pairs_ab.txt)
 #endif
 #ifndef F4_REV
 #define F4_REV 1                       // odd full bands walk upwards (shared halo rows in L2, below)
@@ -54,10 +65,157 @@ static_assert(F4_RB % 6 == 0 && F4_RB > 0, "bands are whole 6-step blocks");
 
 typedef unsigned f4_u2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ void f4_unpack(f4_u2 r, fu_f2& a, fu_f2& b, unsigned hi16) {
-    a = fu_f2{__builtin_bit_cast(float, r.x << 16), __builtin_bit_cast(float, r.x & hi16)};
-    b = fu_f2{__builtin_bit_cast(float, r.y << 16), __builtin_bit_cast(float, r.y & hi16)};
+// the lane's four bf16 columns as the stride-2 f32 pairs p = (c0, c2) and q = (c1, c3)
+__device__ __forceinline__ void f4_unpack(f4_u2 r, fu_f2& p, fu_f2& q, unsigned hi16) {
+    p = fu_f2{__builtin_bit_cast(float, r.x << 16), __builtin_bit_cast(float, r.y << 16)};
+    q = fu_f2{__builtin_bit_cast(float, r.x & hi16), __builtin_bit_cast(float, r.y & hi16)};
 }
+// Packed ops on aligned pairs with a per-lane weight pair (no broadcast): d = w * a and
+// c += w * a, each half an IEEE multiply / fmaf.  Inline asm like fu_pfma: a half of `a` may
+// come from a DPP move (Makefile: compiler-made packed ops on such pairs were wrong).
+__device__ __forceinline__ fu_f2 f4_pmul2(fu_f2 w, fu_f2 a) {
+    fu_f2 d;
+    asm("v_pk_mul_f32 %0, %1, %2" : "=v"(d) : "v"(w), "v"(a));
+    return d;
+}
+__device__ __forceinline__ fu_f2 f4_pfma2(fu_f2 w, fu_f2 a, fu_f2 c) {
+    asm("v_pk_fma_f32 %0, %1, %2, %0" : "+v"(c) : "v"(w), "v"(a));
+    return c;
+}
+// Multi-instruction statements.  Two things about the compiler's hazard recognizer shape them:
+// (1) A DPP operand must be 2 VALU instructions old, and the recognizer does not see an
+//     inline-asm packed op as its writer.  Every statement below reads its DPP operand in its
+//     third instruction or later: safe whatever precedes it (tools/dpp_hazard.py scans the
+//     assembly for it).
+// (2) An asm statement that reads a register an earlier asm statement wrote gets an s_nop
+//     unless a compiler-made instruction lies between the two (asm statements count as no
+//     distance at all), however far apart they are.  Dependent ops that share a statement
+//     cost none, and k_fused4's step is ordered in groups of independent statements with
+//     the step's ordinary instructions (unpacks, loads, stores) between the groups.
+#define F4_SHR_ " wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1"   /* f_prev */
+#define F4_SHL_ " wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1"   /* f_next */
+// The vertical blend of one pair as one statement: a x[r-1] + b x[r] + c x[r+1] with the row
+// weights (a, b) = lxy and (c, .) = lzw broadcast by op_sel; RC 1 has no c term, RC 2 no a term
+// (the ops and their order are k_fused's fu_pmul / fu_pfma chain).
+template <int RC>
+__device__ __forceinline__ fu_f2 f4_vblend(fu_f2 lxy, fu_f2 lzw, fu_f2 xm, fu_f2 x1, fu_f2 xq) {
+    fu_f2 d;
+    if constexpr (RC == 1)
+        asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[0,1]\n\t"
+            "v_pk_fma_f32 %0, %1, %3, %0 op_sel:[1,0,0] op_sel_hi:[1,1,1]"
+            : "=&v"(d) : "v"(lxy), "v"(xm), "v"(x1));
+    else if constexpr (RC == 2)
+        asm("v_pk_mul_f32 %0, %1, %3 op_sel:[1,0] op_sel_hi:[1,1]\n\t"
+            "v_pk_fma_f32 %0, %2, %4, %0 op_sel_hi:[0,1,1]"
+            : "=&v"(d) : "v"(lxy), "v"(lzw), "v"(x1), "v"(xq));
+    else
+        asm("v_pk_mul_f32 %0, %1, %3 op_sel_hi:[0,1]\n\t"
+            "v_pk_fma_f32 %0, %1, %4, %0 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
+            "v_pk_fma_f32 %0, %2, %5, %0 op_sel_hi:[0,1,1]"
+            : "=&v"(d) : "v"(lxy), "v"(lzw), "v"(xm), "v"(x1), "v"(xq));
+    return d;
+}
+// CD 1's horizontal blend (taps q-1, q) of vp = (v0, v2), vq = (v1, v3) as one statement:
+//   uq = w1q * vq + w0q * vp                       (u1, u3: aligned pairs, pk_mul then pk_fma)
+//   up.x = fmaf(w01, v0, w00 * f_prev(v3)),  up.y = fmaf(w11, v2, w10 * v1)
+__device__ __forceinline__ void f4_hblend_prev(fu_f2 w0q, fu_f2 w1q, float w00, float w01,
+                                               float w10, float w11, fu_f2 vp, fu_f2 vq,
+                                               fu_f2& up, fu_f2& uq) {
+    float ux, uy;
+    asm("v_pk_mul_f32 %0, %3, %5\n\t"
+        "v_mul_f32 %2, %9, %13\n\t"
+        "v_fmac_f32 %2, %10, %12\n\t"
+        "v_mul_f32_dpp %1, %14, %7" F4_SHR_ "\n\t"
+        "v_pk_fma_f32 %0, %4, %6, %0\n\t"
+        "v_fmac_f32 %1, %8, %11"
+        : "=&v"(uq), "=&v"(ux), "=&v"(uy)
+        : "v"(w0q), "v"(w1q), "v"(vp), "v"(vq), "v"(w00), "v"(w01), "v"(w10), "v"(w11),
+          "v"(vp.x), "v"(vp.y), "v"(vq.x), "v"(vq.y));
+    up = fu_f2{ux, uy};
+}
+// CD 2's (taps q, q+1):
+//   up = w2p * vq + w1p * vp                       (u0, u2)
+//   uq.x = fmaf(w02, v2, w01 * v1),  uq.y = fmaf(w12, f_next(v0), w11 * v3)
+__device__ __forceinline__ void f4_hblend_next(fu_f2 w1p, fu_f2 w2p, float w01, float w02,
+                                               float w11, float w12, fu_f2 vp, fu_f2 vq,
+                                               fu_f2& up, fu_f2& uq) {
+    float ux, uy;
+    asm("v_pk_mul_f32 %0, %3, %5\n\t"
+        "v_mul_f32 %1, %7, %13\n\t"
+        "v_fmac_f32 %1, %8, %12\n\t"
+        "v_mul_f32 %2, %9, %14\n\t"
+        "v_pk_fma_f32 %0, %4, %6, %0\n\t"
+        "v_fmac_f32_dpp %2, %11, %10" F4_SHL_
+        : "=&v"(up), "=&v"(ux), "=&v"(uy)
+        : "v"(w1p), "v"(w2p), "v"(vp), "v"(vq), "v"(w01), "v"(w02), "v"(w11), "v"(w12),
+          "v"(vp.x), "v"(vp.y), "v"(vq.x), "v"(vq.y));
+    uq = fu_f2{ux, uy};
+}
+// The stencil's pairs that straddle a lane, from up = (u0, u2) and uq = (u1, u3):
+//   ul = (u-1, u1) = (f_prev(uq.y), uq.x)      shift -1
+//   ur = (u2, u4) = (up.y, f_next(up.x))       shifts +1, +2
+//   ur2 = (u3, u5) = (uq.y, f_next(uq.x))      shift +2 (tap column class 0, odd centre rows)
+// NL / NR2: whether this u row's taps read ul / ur2 (an asm statement is not dead code to the
+// compiler).  A row that reads ur2 and not ul makes (ur, ur2); any other (ul, ur) and ur2 if read.
+template <bool NL, bool NR2>
+__device__ __forceinline__ void f4_straddle(fu_f2 up, fu_f2 uq, fu_f2& ul, fu_f2& ur, fu_f2& ur2) {
+    float rx, ry, lx = 0.f, ly = 0.f, sx = 0.f, sy = 0.f;
+    if constexpr (NR2 && NL)
+        asm("v_mov_b32 %0, %7\n\t"
+            "v_mov_b32 %3, %8\n\t"
+            "v_mov_b32_dpp %1, %6" F4_SHL_ "\n\t"
+            "v_mov_b32_dpp %2, %9" F4_SHR_ "\n\t"
+            "v_mov_b32 %4, %9\n\t"
+            "v_mov_b32_dpp %5, %8" F4_SHL_
+            : "=&v"(rx), "=&v"(ry), "=&v"(lx), "=&v"(ly), "=&v"(sx), "=&v"(sy)
+            : "v"(up.x), "v"(up.y), "v"(uq.x), "v"(uq.y));
+    else if constexpr (NR2)
+        asm("v_mov_b32 %0, %5\n\t"
+            "v_mov_b32 %2, %7\n\t"
+            "v_mov_b32_dpp %1, %4" F4_SHL_ "\n\t"
+            "v_mov_b32_dpp %3, %6" F4_SHL_
+            : "=&v"(rx), "=&v"(ry), "=&v"(sx), "=&v"(sy)
+            : "v"(up.x), "v"(up.y), "v"(uq.x), "v"(uq.y));
+    else
+        asm("v_mov_b32 %0, %5\n\t"
+            "v_mov_b32 %3, %6\n\t"
+            "v_mov_b32_dpp %1, %4" F4_SHL_ "\n\t"
+            "v_mov_b32_dpp %2, %7" F4_SHR_
+            : "=&v"(rx), "=&v"(ry), "=&v"(lx), "=&v"(ly)
+            : "v"(up.x), "v"(up.y), "v"(uq.x), "v"(uq.y));
+    ur = fu_f2{rx, ry};
+    ul = fu_f2{lx, ly};
+    ur2 = fu_f2{sx, sy};
+}
+// The folded same-size h2r of one conv row held as za = (z0, z2), zb = (z1, z3), cw = (1/3,
+// neighbour weight).  Even rows: o[b] = z[b+1] / 3 + z[b], the last one's z[b+1] the next lane's
+// z0; odd rows: o[b] = z[b-1] / 3 + z[b], the first one's z[b-1] the previous lane's z3.  The two
+// outputs whose terms are aligned pairs are one packed FMA; the neighbour term is a
+// v_fmac_f32_dpp (as fu_h2r3_even).  Bit-identical to the four fmaf.
+__device__ __forceinline__ void f4_h2r_even(fu_f2 za, fu_f2 zb, fu_f2 cw, float& o0, float& o1,
+                                            float& o2, float& o3) {
+    fu_f2 d;
+    float a, zby = zb.y;
+    asm("v_pk_fma_f32 %0, %3, %5, %4 op_sel_hi:[0,1,1]\n\t"
+        "v_fma_f32 %1, %9, %7, %8\n\t"
+        "v_fmac_f32_dpp %2, %6, %10" F4_SHL_
+        : "=&v"(d), "=&v"(a), "+v"(zby)
+        : "v"(cw), "v"(za), "v"(zb), "v"(za.x), "v"(za.y), "v"(zb.x), "v"(cw.x), "v"(cw.y));
+    o0 = d.x; o1 = a; o2 = d.y; o3 = zby;
+}
+__device__ __forceinline__ void f4_h2r_odd(fu_f2 za, fu_f2 zb, fu_f2 cw, float& o0, float& o1,
+                                           float& o2, float& o3) {
+    fu_f2 d;
+    float a, zax = za.x;
+    asm("v_pk_fma_f32 %0, %3, %4, %5 op_sel_hi:[0,1,1]\n\t"
+        "v_fma_f32 %1, %9, %7, %8\n\t"
+        "v_fmac_f32_dpp %2, %6, %10" F4_SHR_
+        : "=&v"(d), "=&v"(a), "+v"(zax)
+        : "v"(cw), "v"(za), "v"(zb), "v"(zb.y), "v"(zb.x), "v"(za.y), "v"(cw.x), "v"(cw.y));
+    o0 = zax; o1 = d.x; o2 = a; o3 = d.y;
+}
+#undef F4_SHR_
+#undef F4_SHL_
 
 // rect -> hex -> HexConv2d -> hex -> rect (the headline); OP = the stencil's tap column class
 // at padding 1 ((even_odd_offset + 1) & 1).
@@ -73,7 +231,7 @@ __device__ __forceinline__ void f4_unpack(f4_u2 r, fu_f2& a, fu_f2& b, unsigned 
 // taps first and its above taps last: the same products, summed in another order (fp32
 // rounding level; the bias still comes first).
 template <int OP>
-__global__ __launch_bounds__(F4_THREADS) __attribute__((amdgpu_waves_per_eu(F4_WPE)))
+__global__ __launch_bounds__(F4_THREADS) __attribute__((amdgpu_waves_per_eu(F4_WPE, F4_WPE)))
 void k_fused4(const __bf16* __restrict__ x, const float* __restrict__ kern,
               const float* __restrict__ bias, __bf16* __restrict__ y, FusedGeom F) {
     constexpr int C = 3, O = 3;
@@ -93,7 +251,7 @@ void k_fused4(const __bf16* __restrict__ x, const float* __restrict__ kern,
     if (b >= F.B) return;                            // uniform per workgroup
     const int win = grp * F4_GW + wslot;             // may be >= nwin: runs, owns nothing
     const int W0 = win * F4_OWN - F4_HL;
-    const int ce = W0 + 4 * lane;                    // columns ce .. ce + 3 (pairs A, B)
+    const int ce = W0 + 4 * lane;                    // columns ce .. ce + 3 (pairs P, Q)
     const int s0 = band * RB;
     const int s1 = min(s0 + RB, F.h2);
     const bool up = F4_REV && (band & 1) && s1 - s0 == RB;   // uniform
@@ -158,6 +316,13 @@ void k_fused4(const __bf16* __restrict__ x, const float* __restrict__ kern,
     const bool any_r = __builtin_amdgcn_ballot_w64(we[0][2] != 0.f || wo[0][2] != 0.f ||
                                                    we[1][2] != 0.f || wo[1][2] != 0.f) != 0;
     const int cd = !any_r ? 1 : (!any_l ? 2 : 0);
+    // the same weights as stride-2 pairs: tap t of columns (ce, ce + 2) and (ce + 1, ce + 3)
+    fu_f2 WE[3], WO[3];
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+        WE[t] = fu_f2{we[0][t], we[1][t]};
+        WO[t] = fu_f2{wo[0][t], wo[1][t]};
+    }
 
     // owned lanes 2 .. 61 (w2 % 4 == 0: a lane is wholly inside or outside the raster)
     const bool own = lane >= F4_HL / 4 && lane < (F4_HL + F4_OWN) / 4 && ce >= 0 && ce < F.w2 &&
@@ -203,10 +368,11 @@ void k_fused4(const __bf16* __restrict__ x, const float* __restrict__ kern,
     }
     float c13 = 1.f / 3.f;
     asm volatile("" : "+v"(c13));
-    // h2r neighbours outside the raster (:303-323): pair B's right neighbour (even rows) and
-    // pair A's left neighbour (odd rows); the inner ones are always inside
+    // h2r neighbours outside the raster (:303-323): column ce + 3's right neighbour (even rows) and
+    // column ce's left neighbour (odd rows); the inner ones are always inside
     const float wn_f = (ce + 4 < F.w2) ? c13 : 0.f;
     const float wp_f = (ce - 1 >= 0) ? c13 : 0.f;
+    const fu_f2 c13n = {c13, wn_f}, c13p = {c13, wp_f};   // (1/3, neighbour weight) pairs
     unsigned hi16 = 0xffff0000u;
     asm volatile("" : "+v"(hi16));
 
@@ -222,8 +388,8 @@ void k_fused4(const __bf16* __restrict__ x, const float* __restrict__ kern,
         // row-table entry of u row row(j)
         auto lut_e = [&](int j) { return UP ? RB - j : j + 1; };
         f4_u2 raw[6][C];                    // rect rows in flight, slot k % 6
-        fu_f2 XA[3][C], XB[3][C];           // rect rows as f32 pairs A / B, slot k % 3
-        fu_f2 ZA[3][O], ZB[3][O];           // conv rows being accumulated, slot k % 3
+        fu_f2 XA[3][C], XB[3][C];           // rect rows as f32 pairs P / Q, slot k % 3
+        fu_f2 ZA[3][O], ZB[3][O];           // conv rows being accumulated, columns (0, 2) / (1, 3)
 
         // live false: the loads return zeros without a memory access (an offset past the buffer)
         auto issue = [&](auto SLc, int r, bool live = true) {
@@ -243,7 +409,16 @@ void k_fused4(const __bf16* __restrict__ x, const float* __restrict__ kern,
         // S2), scattered into conv rows row(PH+2) (started here with the bias: slot S2), row(PH+1)
         // (centre: S1) and row(PH) (completed here: S0).  Downwards the started row is the one
         // below (u row = its 'above' row: taps 0, 1), upwards the one above (taps 5, 6).
-        auto urow = [&](auto PHc, float4 L, auto CENc, auto BELc) {
+        //
+        // Order (see "Multi-instruction statements" above): groups of independent asm statements,
+        // fenced by scheduling barriers, with the step's compiler-made instructions between them,
+        // which the caller supplies: pre(c) before channel c's vertical blend (its unpack),
+        // mid(i), i = 0 .. 5, between the tap groups (its loads), fin() once the completed
+        // row's taps are done (its h2r), put(o) after each of the last three groups (its stores).  The channels are skewed by one stage (blend, horizontal blend, straddling
+        // pairs); the taps go level by level: group l holds every accumulator's l-th tap of this
+        // u row, so each accumulator still takes its taps in channel and tap order.
+        auto urow = [&](auto PHc, float4 L, auto CENc, auto BELc, auto&& pre, auto&& mid, auto&& fin,
+                        auto&& put) {
             constexpr int PH = decltype(PHc)::value;
             constexpr bool CEN = decltype(CENc)::value, BEL = decltype(BELc)::value;
             constexpr int S0 = fu_mod(PH, 3), S1 = fu_mod(PH + 1, 3), S2 = fu_mod(PH + 2, 3);
@@ -253,108 +428,112 @@ void k_fused4(const __bf16* __restrict__ x, const float* __restrict__ kern,
             // UP band, s1 are even
             constexpr int PB = UP ? fu_mod(PH + 1, 2) : fu_mod(PH, 2), PC = 1 - PB;
             constexpr int TN = UP ? 5 : 0, TD = UP ? 0 : 5;   // first tap of started / completed row
+            // which straddling pairs this u row's taps read: shift -1 reads UL, shift +2 reads UR2
+            constexpr auto reads = [](int s) {
+                bool r = fu_tap_shift(TN, PB, OP) == s || fu_tap_shift(TN + 1, PB, OP) == s;
+                if (BEL) r = r || fu_tap_shift(TD, PB, OP) == s || fu_tap_shift(TD + 1, PB, OP) == s;
+                if (CEN) r = r || fu_tap_shift(2, PC, OP) == s || fu_tap_shift(3, PC, OP) == s ||
+                             fu_tap_shift(4, PC, OP) == s;
+                return r;
+            };
+            constexpr bool NEED_L = reads(-1), NEED_R2 = reads(2);
             const fu_f2 Lxy = {L.x, L.y}, Lzw = {L.z, L.w};
-            fu_sfor<0, C>([&](auto Cc) {
+            fu_f2 VP[C], VQ[C];                 // vertical blends of the P / Q pairs
+            // the u row: columns ce .. ce+3 as UP = (u0, u2), UQ = (u1, u3), and the stencil's
+            // operands that straddle a lane, UR = (u2, u4), UL = (u-1, u1), UR2 = (u3, u5):
+            // accumulator ZA = (z0, z2) reads (u[s], u[s+2]), ZB = (z1, z3) reads (u[s+1], u[s+3])
+            fu_f2 UP_[C], UQ_[C], UR[C], UL[C], UR2[C];
+            auto fence = [] { __builtin_amdgcn_sched_barrier(0); };
+            auto vblend = [&](auto Cc) {
                 constexpr int c = decltype(Cc)::value;
-                float ue[2], uo[2];
-                // vertical blend, packed (as k_fused), for both pairs: a x[r-1] + b x[r] + c x[r+1]
-                auto vblend = [&](const fu_f2 (&X)[3][C]) {
-                    if constexpr (RC == 1) return fu_pfma<1, false>(Lxy, X[S1][c], fu_pmul<0>(Lxy, X[XM][c]));
-                    else if constexpr (RC == 2) return fu_pfma<0, false>(Lzw, X[XQ][c], fu_pmul<1>(Lxy, X[S1][c]));
-                    else return fu_pfma<0, false>(Lzw, X[XQ][c], fu_pfma<1, false>(Lxy, X[S1][c], fu_pmul<0>(Lxy, X[XM][c])));
-                };
-                const fu_f2 VA = vblend(XA), VB = vblend(XB);
-                // horizontal blend: columns ce .. ce+3 = VA.x VA.y VB.x VB.y; the lane's left
-                // neighbour column is the previous lane's VB.y, its right one the next lane's VA.x
+                VP[c] = f4_vblend<RC>(Lxy, Lzw, XA[XM][c], XA[S1][c], XA[XQ][c]);
+                VQ[c] = f4_vblend<RC>(Lxy, Lzw, XB[XM][c], XB[S1][c], XB[XQ][c]);
+            };
+            // horizontal blend: the lane's left neighbour column is the previous lane's VQ.y,
+            // its right one the next lane's VP.x; where both columns of a pair take their terms
+            // from aligned pairs the blend is packed (pk_mul then pk_fma: the rounding of
+            // fmaf(w1, v, w0 * v'))
+            auto hblend = [&](auto Cc) {
+                constexpr int c = decltype(Cc)::value;
+                const fu_f2 vp = VP[c], vq = VQ[c];
                 if constexpr (CD == 1) {            // taps q-1, q
-                    ue[0] = fmaf(we[0][1], VA.x, we[0][0] * f_prev(VB.y));
-                    uo[0] = fmaf(wo[0][1], VA.y, wo[0][0] * VA.x);
-                    ue[1] = fmaf(we[1][1], VB.x, we[1][0] * VA.y);
-                    uo[1] = fmaf(wo[1][1], VB.y, wo[1][0] * VB.x);
+                    f4_hblend_prev(WO[0], WO[1], we[0][0], we[0][1], we[1][0], we[1][1], vp, vq,
+                                   UP_[c], UQ_[c]);
                 } else if constexpr (CD == 2) {     // taps q, q+1
-                    ue[0] = fmaf(we[0][2], VA.y, we[0][1] * VA.x);
-                    uo[0] = fmaf(wo[0][2], VB.x, wo[0][1] * VA.y);
-                    ue[1] = fmaf(we[1][2], VB.y, we[1][1] * VB.x);
-                    uo[1] = fmaf(wo[1][2], f_next(VA.x), wo[1][1] * VB.y);
+                    f4_hblend_next(WE[1], WE[2], wo[0][1], wo[0][2], wo[1][1], wo[1][2], vp, vq,
+                                   UP_[c], UQ_[c]);
                 } else {
-                    const float pl = f_prev(VB.y), nx = f_next(VA.x);
-                    ue[0] = fmaf(we[0][2], VA.y, fmaf(we[0][1], VA.x, we[0][0] * pl));
-                    uo[0] = fmaf(wo[0][2], VB.x, fmaf(wo[0][1], VA.y, wo[0][0] * VA.x));
-                    ue[1] = fmaf(we[1][2], VB.y, fmaf(we[1][1], VB.x, we[1][0] * VA.y));
-                    uo[1] = fmaf(wo[1][2], nx, fmaf(wo[1][1], VB.y, wo[1][0] * VB.x));
+                    const fu_f2 tl = {we[0][0] * f_prev(vq.y), we[1][0] * vq.x};
+                    UP_[c] = f4_pfma2(WE[2], vq, f4_pfma2(WE[1], vp, tl));
+                    const fu_f2 tq = f4_pfma2(WO[1], vq, f4_pmul2(WO[0], vp));
+                    UQ_[c] = fu_f2{fmaf(wo[0][2], vp.y, tq.x), fmaf(wo[1][2], f_next(vp.x), tq.y)};
                 }
-                // the stencil's column-shifted pairs (u[ce+s], u[ce+1+s]) for both pairs:
-                // s = 0: own; s = 1: (uo_k, ue_{k+1}); s = -1: (uo_{k-1}, ue_k); s = 2: pair k+1
-                const float nue = f_next(ue[0]);                 // next lane's u[ce + 4]
-                const fu_f2 U0[2] = {fu_f2{ue[0], uo[0]}, fu_f2{ue[1], uo[1]}};
-                const fu_f2 U1[2] = {fu_f2{uo[0], ue[1]}, fu_f2{uo[1], nue}};
-                const fu_f2 Um[2] = {fu_f2{f_prev(uo[1]), ue[0]}, fu_f2{uo[0], ue[1]}};
-                const fu_f2 U2[2] = {U0[1], fu_f2{nue, OP == 0 ? f_next(uo[0]) : 0.f}};
+            };
+            auto straddle = [&](auto Cc) {
+                constexpr int c = decltype(Cc)::value;
+                f4_straddle<NEED_L, NEED_R2>(UP_[c], UQ_[c], UL[c], UR[c], UR2[c]);
+            };
+            // tap T of channel c into the conv row in slot SL (parity PAR), every output channel
+            auto tap = [&](auto SLc, auto PARc, auto Cc, auto Tc, auto BIASc) {
+                constexpr int SL = decltype(SLc)::value, PAR = decltype(PARc)::value;
+                constexpr int c = decltype(Cc)::value, T = decltype(Tc)::value;
+                constexpr int s = fu_tap_shift(T, PAR, OP);
+                const fu_f2 aA = s == -1 ? UL[c] : (s == 0 ? UP_[c] : (s == 1 ? UQ_[c] : UR[c]));
+                const fu_f2 aB = s == -1 ? UP_[c] : (s == 0 ? UQ_[c] : (s == 1 ? UR[c] : UR2[c]));
                 fu_sfor<0, O>([&](auto OOc) {
                     constexpr int o = decltype(OOc)::value;
-                    constexpr int j0 = (o * C + c) * 7;
-                    auto tapk = [&](auto Tc, fu_f2& zA, fu_f2& zB, int par) {
-                        constexpr int j = j0 + decltype(Tc)::value;
-                        constexpr bool WS = (j >> 1) < NWS;
-                        const int s = fu_tap_shift(decltype(Tc)::value, par, OP);
-                        const fu_f2 aA = s == -1 ? Um[0] : (s == 0 ? U0[0] : (s == 1 ? U1[0] : U2[0]));
-                        const fu_f2 aB = s == -1 ? Um[1] : (s == 0 ? U0[1] : (s == 1 ? U1[1] : U2[1]));
-                        zA = fu_pfma<j & 1, WS>(wkp[j >> 1], aA, zA);
-                        zB = fu_pfma<j & 1, WS>(wkp[j >> 1], aB, zB);
-                    };
-                    if constexpr (c == 0) {       // the first tap of the started row adds the bias
-                        constexpr int jb = j0 + TN;
-                        constexpr bool WS = (jb >> 1) < NWS;
-                        const int s = fu_tap_shift(TN, PB, OP);
-                        const fu_f2 aA = s == -1 ? Um[0] : (s == 0 ? U0[0] : (s == 1 ? U1[0] : U2[0]));
-                        const fu_f2 aB = s == -1 ? Um[1] : (s == 0 ? U0[1] : (s == 1 ? U1[1] : U2[1]));
-                        ZA[S2][o] = fu_pfma_b<jb & 1, o & 1, WS>(wkp[jb >> 1], aA, bvp[o >> 1]);
-                        ZB[S2][o] = fu_pfma_b<jb & 1, o & 1, WS>(wkp[jb >> 1], aB, bvp[o >> 1]);
+                    constexpr int j = (o * C + c) * 7 + T;
+                    constexpr bool WS = (j >> 1) < NWS;
+                    if constexpr (decltype(BIASc)::value) {   // a started row's first tap adds the bias
+                        ZA[SL][o] = fu_pfma_b<j & 1, o & 1, WS>(wkp[j >> 1], aA, bvp[o >> 1]);
+                        ZB[SL][o] = fu_pfma_b<j & 1, o & 1, WS>(wkp[j >> 1], aB, bvp[o >> 1]);
                     } else {
-                        tapk(IC<TN>{}, ZA[S2][o], ZB[S2][o], PB);
-                    }
-                    tapk(IC<TN + 1>{}, ZA[S2][o], ZB[S2][o], PB);
-                    if constexpr (CEN) {
-                        tapk(IC<2>{}, ZA[S1][o], ZB[S1][o], PC);
-                        tapk(IC<3>{}, ZA[S1][o], ZB[S1][o], PC);
-                        tapk(IC<4>{}, ZA[S1][o], ZB[S1][o], PC);
-                    }
-                    if constexpr (BEL) {
-                        tapk(IC<TD>{}, ZA[S0][o], ZB[S0][o], PB);
-                        tapk(IC<TD + 1>{}, ZA[S0][o], ZB[S0][o], PB);
+                        ZA[SL][o] = fu_pfma<j & 1, WS>(wkp[j >> 1], aA, ZA[SL][o]);
+                        ZB[SL][o] = fu_pfma<j & 1, WS>(wkp[j >> 1], aB, ZB[SL][o]);
                     }
                 });
-            });
-        };
-
-        // conv row row(PH) (slot PH % 3) -> output row row(PH) (the folded same-size h2r: even
-        // rows z'[b] + z'[b+1] / 3, odd rows z'[b-1] / 3 + z'[b], geometry_np.py:347-354)
-        auto out_row = [&](auto PHc, int k) {
-            constexpr int PH = decltype(PHc)::value;
-            constexpr int S0 = PH % 3;
-            constexpr int PAR = UP ? (PH + 1) & 1 : PH & 1;
-            const unsigned so = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)row(k) * yrow));
-#pragma unroll
-            for (int o = 0; o < O; ++o) {
-                const fu_f2 zA = ZA[S0][o], zB = ZB[S0][o];
-                float o0, o1, o2, o3;
-                if constexpr (PAR == 0) {
-                    o0 = fmaf(c13, zA.y, zA.x);
-                    o1 = fmaf(c13, zB.x, zA.y);
-                    o2 = fmaf(c13, zB.y, zB.x);
-                    o3 = fmaf(wn_f, f_next(zA.x), zB.y);
-                } else {
-                    o0 = fmaf(wp_f, f_prev(zB.y), zA.x);
-                    o1 = fmaf(c13, zA.x, zA.y);
-                    o2 = fmaf(c13, zA.y, zB.x);
-                    o3 = fmaf(c13, zB.x, zB.y);
+            };
+            // level l: the started and completed rows take 2 taps per channel, the centre row 3
+            auto level = [&](auto Lc) {
+                constexpr int l = decltype(Lc)::value;
+                if constexpr (l < 2 * C) {
+                    tap(IC<S2>{}, IC<PB>{}, IC<l / 2>{}, IC<TN + l % 2>{}, std::bool_constant<l == 0>{});
+                    if constexpr (BEL)
+                        tap(IC<S0>{}, IC<PB>{}, IC<l / 2>{}, IC<TD + l % 2>{}, std::false_type{});
                 }
-                typedef __bf16 t2v __attribute__((ext_vector_type(2)));
-                const f4_u2 v = {__builtin_bit_cast(unsigned, t2v{(__bf16)o0, (__bf16)o1}),
-                                 __builtin_bit_cast(unsigned, t2v{(__bf16)o2, (__bf16)o3})};
-                __builtin_amdgcn_raw_buffer_store_b64(v, yrs, yoff, so + o * yplane, 0);
-            }
+                if constexpr (CEN)
+                    tap(IC<S1>{}, IC<PC>{}, IC<l / 3>{}, IC<2 + l % 3>{}, std::false_type{});
+            };
+            static_assert(C == 3, "the stage skew below is written out for three channels");
+            fence(); pre(IC<0>{});
+            fence(); vblend(IC<0>{});
+            fence(); pre(IC<1>{});
+            fence(); hblend(IC<0>{}); vblend(IC<1>{});
+            fence(); pre(IC<2>{});
+            fence(); straddle(IC<0>{}); hblend(IC<1>{}); vblend(IC<2>{});
+            fence(); mid(IC<0>{});
+            fence(); level(IC<0>{}); straddle(IC<1>{}); hblend(IC<2>{});
+            fence(); mid(IC<1>{});
+            fence(); level(IC<1>{}); straddle(IC<2>{});
+            fence(); mid(IC<2>{});
+            fence(); level(IC<2>{});
+            fence(); mid(IC<3>{});
+            fence(); level(IC<3>{});
+            fence(); mid(IC<4>{});
+            fence(); level(IC<4>{});
+            fence(); mid(IC<5>{});
+            fence(); level(IC<5>{});             // the completed row's last taps
+            fence(); fin();
+            fence(); level(IC<6>{});
+            fence(); put(IC<0>{});
+            fence(); level(IC<7>{});
+            fence(); put(IC<1>{});
+            fence(); level(IC<8>{});
+            fence(); put(IC<2>{});
+            fence();
         };
+        auto no1 = [](auto) {};             // the prologue's u rows: nothing to interleave
+        auto no0 = [] {};
 
         // ---- prologue: u rows row(-1) and row(0) ----------------------------------------
         {
@@ -381,25 +560,65 @@ void k_fused4(const __bf16* __restrict__ x, const float* __restrict__ kern,
                 f4_unpack(t2[c], XA[0][c], XB[0][c], hi16);   // row(0)  -> slot 0
             }
         }
-        urow(IC<-2>{}, lut[lut_e(-1)], std::false_type{}, std::false_type{});   // u row(-1): start only
+        urow(IC<-2>{}, lut[lut_e(-1)], std::false_type{}, std::false_type{}, no1, no1, no0, no1);   // u row(-1): start only
         convert(IC<1>{}, IC<1>{});                                              // row(1) -> slot 1
-        urow(IC<-1>{}, lut[lut_e(0)], std::true_type{}, std::false_type{});     // u row(0): start, centre
+        urow(IC<-1>{}, lut[lut_e(0)], std::true_type{}, std::false_type{}, no1, no1, no0, no1);     // u row(0): start, centre
         __builtin_amdgcn_s_waitcnt(0x0f70);                                     // vmcnt(0)
 
         // ---- main loop -----------------------------------------------------------------
         const int n = s1 - s0;
         float4 lnext = lut[lut_e(1)];
+        unsigned lso = row_off(row(min(2 + PD, n + 1)));        // load offset of the next step's row
+        // One step: rect row row(k+2) unpacked, row(k+2+PD) requested, u row row(k+1) made and
+        // scattered, conv row row(k) through the folded same-size h2r (even rows z'[b] +
+        // z'[b+1] / 3, odd rows z'[b-1] / 3 + z'[b], geometry_np.py:347-354) and stored.
         auto step = [&](auto PHc, int k) {
             constexpr int PH = decltype(PHc)::value;
-            __builtin_amdgcn_sched_barrier(0);
-            convert(IC<(PH + 2) % 6>{}, IC<(PH + 2) % 3>{});            // rect row row(k+2)
-            // (a row past the band's last halo row is never read: its load goes out of range,
-            // no memory access, instead of a 31st row from HBM)
-            issue(IC<(PH + 2 + PD) % 6>{}, row(min(k + 2 + PD, n + 1)), k + 2 + PD <= n + 1);
+            constexpr int RS = (PH + 2) % 6, XS = (PH + 2) % 3, LS = (PH + 2 + PD) % 6;
+            constexpr int S0 = PH % 3;
+            constexpr int PAR = UP ? (PH + 1) & 1 : PH & 1;
             const float4 L = lnext;
-            lnext = lut[min(max(lut_e(k + 2), 0), NLUT - 1)];
-            urow(PHc, L, std::true_type{}, std::true_type{});           // u row row(k+1)
-            out_row(PHc, k);
+            float ov[O][4];
+            unsigned lvo = 0, sso = 0;
+            int nrow = 0;
+            auto pre = [&](auto Cc) {                   // rect row row(k+2), channel c
+                constexpr int c = decltype(Cc)::value;
+                f4_unpack(raw[RS][c], XA[XS][c], XB[XS][c], hi16);
+            };
+            auto mid = [&](auto Ic) {
+                constexpr int i = decltype(Ic)::value;
+                if constexpr (i == 0) {
+                    // (a row past the band's last halo row is never read: its load goes out of
+                    // range, no memory access, instead of a 31st row from HBM)
+                    lvo = k + 2 + PD <= n + 1 ? xoff : 0x80000000u;
+                }
+                if constexpr (i < C)
+                    raw[LS][i] = __builtin_amdgcn_raw_buffer_load_b64(xrs, lvo, lso + i * xplane, 0);
+                if constexpr (i == 3) lnext = lut[min(max(lut_e(k + 2), 0), NLUT - 1)];
+                // the next step's load offset, a piece at a time (scalar instructions for the
+                // places that have nothing else to put between two groups)
+                if constexpr (i == 4) nrow = row(min(k + 3 + PD, n + 1));
+                if constexpr (i == 5) nrow = min(max(nrow, 0), F.h - 1);
+            };
+            auto fin = [&] {
+                lso = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)nrow * xrow));
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int o = 0; o < O; ++o) {
+                    if constexpr (PAR == 0) f4_h2r_even(ZA[S0][o], ZB[S0][o], c13n, ov[o][0], ov[o][1], ov[o][2], ov[o][3]);
+                    else f4_h2r_odd(ZA[S0][o], ZB[S0][o], c13p, ov[o][0], ov[o][1], ov[o][2], ov[o][3]);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                sso = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)row(k) * yrow));
+            };
+            auto put = [&](auto Oc) {
+                constexpr int o = decltype(Oc)::value;
+                typedef __bf16 t2v __attribute__((ext_vector_type(2)));
+                const f4_u2 v = {__builtin_bit_cast(unsigned, t2v{(__bf16)ov[o][0], (__bf16)ov[o][1]}),
+                                 __builtin_bit_cast(unsigned, t2v{(__bf16)ov[o][2], (__bf16)ov[o][3]})};
+                __builtin_amdgcn_raw_buffer_store_b64(v, yrs, yoff, sso + o * yplane, 0);
+            };
+            urow(PHc, L, std::true_type{}, std::true_type{}, pre, mid, fin, put);
         };
         auto block6 = [&](int base) {
             step(IC<0>{}, base);

@@ -1,8 +1,9 @@
 """Interleaved A/B timing of fused-kernel variants in ONE process (same GPU, same clocks):
 each round launches every variant library three times back to back (the last launch is
 timed) in a shuffled order on the same device buffers; reports the median / min per-launch
-time over the rounds (HIP events on the launch stream) and the median of the per-round
-ratios to the first variant named.
+time over the rounds (HIP events on the launch stream), the median of the per-round
+ratios to the first variant named and their spread (half the interquartile range): naming
+the same library twice gives the spread a real difference has to clear.
 
 usage: python tools/ab_fused.py [rounds] name1 name2 ...   (name 'base' = the in-tree lib;
        others = HyGrid/_lib/variants/libhygrid_<name>.so); env AB_BATCH (default 128).
@@ -79,9 +80,10 @@ def main():
     alg = 2.0 * B * C * H * W * 2
     for n in names:
         t = times[n]
+        q = statistics.quantiles(ratios[n], n=4) if len(ratios[n]) > 1 else [1.0, 1.0, 1.0]
         print(f"{n:14s} median {statistics.median(t):.4f} ms  min {min(t):.4f} ms  "
               f"{alg / statistics.median(t) / 1e6:.0f} GB/s  vs {names[0]} {statistics.median(ratios[n]):.4f}  "
-              f"checksum {sums[n]:.6e}", flush=True)
+              f"spread {(q[2] - q[0]) / 2:.4f}  checksum {sums[n]:.6e}", flush=True)
 
 
 if __name__ == "__main__":
