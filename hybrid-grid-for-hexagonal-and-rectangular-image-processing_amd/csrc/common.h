@@ -100,10 +100,11 @@ template <typename A>
 __device__ __forceinline__ A epi_apply(A v, int o, const Epilogue& e) {
     if (e.scale) v = v * static_cast<const A*>(e.scale)[o];
     if (e.shift) v = v + static_cast<const A*>(e.shift)[o];
+    // torch's rules: ReLU / ReLU6 are clamps, which keep a NaN (`v > 0 ? v : 0` would erase it)
     switch (e.act) {
-    case HG_ACT_RELU: return v > (A)0 ? v : (A)0;
+    case HG_ACT_RELU: return v < (A)0 ? (A)0 : v;
     case HG_ACT_LEAKY_RELU: return v > (A)0 ? v : v * (A)e.slope;
-    case HG_ACT_RELU6: return v > (A)0 ? (v < (A)6 ? v : (A)6) : (A)0;
+    case HG_ACT_RELU6: return v < (A)0 ? (A)0 : (v > (A)6 ? (A)6 : v);
     case HG_ACT_SIGMOID: return (A)1 / ((A)1 + exp(-v));
     case HG_ACT_TANH: return tanh(v);
     default: return v;

@@ -28,6 +28,7 @@ import zlib
 import numpy as np
 import torch
 
+from conv_epilogue_cases import epilogue_ref
 from oracle import oracle as O
 
 BF16, F16, F32, F64, U8 = torch.bfloat16, torch.float16, torch.float32, torch.float64, torch.uint8
@@ -130,21 +131,12 @@ def _np(t):
 
 def reference(case, t):
     """fp64: the oracle conv on the inputs as rounded to their dtypes, then the affine and the
-    activation in NumPy (tests/placement_cases.py::conv's ref)."""
+    activation in NumPy (tests/conv_epilogue_cases.py::epilogue_ref, every hg_act)."""
     y = O.hexconv2d(_np(t["x"]), _np(t["k"]), _np(t["b"]), case.off, case.r, case.s, case.p,
                     case.d, case.g, case.mode, case.pv)
     if case.epi is not None:
         _, _, act, slope = case.epi
-        if t["scale"] is not None:
-            y = y * _np(t["scale"])[None, :, None, None]
-        if t["shift"] is not None:
-            y = y + _np(t["shift"])[None, :, None, None]
-        if act == LEAKY:
-            y = np.where(y >= 0, y, slope * y)
-        elif act == SIGMOID:
-            y = 1.0 / (1.0 + np.exp(-y))
-        elif act != NONE:
-            raise NotImplementedError(act)
+        y = epilogue_ref(y, _np(t["scale"]), _np(t["shift"]), act, slope)
     return y
 
 
