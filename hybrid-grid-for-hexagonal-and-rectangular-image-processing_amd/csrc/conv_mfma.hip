@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <climits>
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 #include "conv_mfma.h"
@@ -29,9 +30,229 @@
 
 namespace hg {
 
-#ifndef CM_TD
-#define CM_TD 1                             // MFMA kernels, 16-bit outputs: D as [column][channel] (below)
-#endif
+// ---- what the kernels share ----------------------------------------------------------------
+// Each step below exists once; a kernel picks its variant by template integers and types only
+// (NOT / NQT tiles, channels per chunk CC, the transposed-D flag TD, the P slot's stride S).
+// k_hexconv_mfma_bf16, k_hexconv_mfma_s2 and k_hexconv_mfma_bf16_s2 are built from them, and
+// k_wsplit_bf16 from cb_split_w.  Not shared:
+//  * one-offs: the DMA issue lambdas, the two fp32 P stagers (cm_stage_p in conv_mfma.h,
+//    cs_stage_p) and the stride-2 bf16 P stager;
+//  * the two MFMA loops (f32 and bf16): as force-inlined helpers they took a wave per SIMD from
+//    the NOT = 2 kernels (profiles/conv_mfma_refactor_resources.txt);
+//  * k_hexconv_mfma and k_hexconv_mfma_bf16d, which keep their own text throughout: built from
+//    the shared steps they kept their registers and waves but ran 0.5-1.3 % slower on four
+//    stride-1 shapes (profiles/conv_mfma_refactor_ab.txt).  A fix to a shared step has to be
+//    made in these two as well.
+
+// CM_TD: the MFMAs take the P fragment as A and the weights as B, so D is [column][channel]:
+// a lane's 4 registers are 4 adjacent output columns of one channel (one 8-B store for
+// 16-bit outputs instead of four 2-B stores); the same products summed in the same order.
+// 16-bit outputs only (fp32 outputs as two 8-B stores: 3.9 % slower than 2-B stores,
+// profiles/r06/conv_mfma_transposed_d_ab.txt).  k_hexconv_mfma_bf16 (the A/B fallback of the
+// DMA kernel) never had the path and passes TD = false.
+constexpr bool CM_TD = true;
+template <typename Tout>
+constexpr bool cm_td = CM_TD && sizeof(Tout) == 2;
+
+constexpr int CM_NQT = CM_Q / 16;           // 16-column tiles per workgroup
+
+typedef __bf16 cm_b8 __attribute__((ext_vector_type(8)));
+typedef unsigned cm_u4 __attribute__((ext_vector_type(4)));
+// The bf16 kernels' weight-fragment LDS layout: channel o's four k-group fragments (16 B each)
+// in a rotated order, so each of ds_read_b128's four 16-lane groups ({0-3,12-15,20-27},
+// {4-11,16-19,28-31}, and the same + 32: MI355X_MICROARCH.md section LDS) reads 16 distinct
+// 16-B bank slots; the plain order o * 4 + g put lanes li and li + 12 (and li + 4, li + 8) of a
+// group on one slot (2-way conflicts; r04 session O counters: 39 % of the LDS cycles).
+__host__ __device__ constexpr int cd_wslot(int o, int g) { return (g + 2 * ((o & 15) >> 2)) & 3; }
+
+constexpr int CB_PP = CM_PP;                // staged columns: cm_pslot<1> serves both P layouts
+constexpr int CB_PSZ = CM_PR * CB_PP + 1;   // P fragments per chunk (+1: the zero fragment)
+constexpr int CSB_PSZ = CS_PR * CS_PP + 1;  // ... at stride 2
+
+// Input channels per LDS chunk of k_hexconv_mfma_s2: 4 (20.7 KB of P + 7.4 KB of weights = 28.2 KB,
+// 3-4 waves per SIMD) against 8 (56.3 KB, 2 workgroups per CU): 4.55 against 5.90 ms on
+// 64 -> 128 1080p b4 f32, 0.264 / 0.397 ms on the 3 -> 64 stem, 0.230 / 0.346 ms on 16 -> 16
+// 540p b8, 2.40 / 3.07 ms on 128 -> 256 540p b2 (profiles/conv_mfma_stride2_ab.txt): as at
+// stride 1, occupancy, not barrier count, is what the staging latency needs.
+constexpr int CS_CC = 4;
+static_assert(CS_CC % 4 == 0 && CS_CC <= CM_CC, "chunk: whole MFMA k quads, the weight stride's rows");
+
+// Where a wave's tap (dy, dk) starts in a staged P channel, in slots: stride 1 row wv + dy,
+// column dk; stride 2 row 2 wv + dy of the two column-parity planes (conv_mfma.h): plane
+// dk & 1, slot dk >> 1.  The 16 columns of a fragment are the 16 slots from there.
+__device__ __forceinline__ int cs_slot(int row, int dk) {     // staged (row, column 2 q' + dk) at q' = 0
+    return row * CS_PP + (dk & 1) * CS_PL + (dk >> 1);
+}
+template <int S>
+__device__ __forceinline__ int cm_pslot(int wv, int dy, int dk) {
+    static_assert(S == 1 || S == 2, "stride");
+    return S == 1 ? (wv + dy) * CM_PP + dk : cs_slot(2 * wv + dy, dk);
+}
+
+// Which tile of which image a workgroup computes, and this lane's place in the fragments.
+template <int NOT>
+struct CmBlock {
+    int tid, wv;                // thread; wave = row of the tile (uniform)
+    int64_t b;                  // image
+    int q0, r0, o0;             // first output column / row / channel of the tile
+    int r, par;                 // this wave's output row and its parity
+    int li, lk;                 // fragment row (or column), k group of this lane
+    __device__ __forceinline__ explicit CmBlock(const MfmaGeom& G) {
+        tid = threadIdx.x;
+        wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+        unsigned bid = xcd_swizzle(blockIdx.x, gridDim.x);
+        const int tq = (int)(bid % G.ntq); bid /= G.ntq;
+        const int tr = (int)(bid % G.ntr); bid /= G.ntr;
+        const int to = (int)(bid % G.nto);
+        b = bid / G.nto;
+        q0 = tq * CM_Q; r0 = tr * CM_ROWS; o0 = to * (16 * NOT);
+        r = r0 + wv;
+        par = r & 1;
+        const int lane = tid & 63;
+        li = lane & 15; lk = lane >> 4;
+    }
+};
+
+// The accumulators start at the bias.  Plain D: register v of lane (li, lk) is channel
+// 4 lk + v of the tile; TD: D is [column][channel], every register is channel li.
+template <bool TD, int NOT, int NQT>
+__device__ __forceinline__ void cm_bias_init(cm_f4 (&acc)[NOT][NQT], const float* __restrict__ bias,
+                                             const MfmaGeom& G, int o0, int li, int lk) {
+#pragma unroll
+    for (int ot = 0; ot < NOT; ++ot) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int o = o0 + ot * 16 + (TD ? li : lk * 4 + v);
+            const float bv = (bias && o < G.O) ? bias[o] : 0.f;
+#pragma unroll
+            for (int qt = 0; qt < NQT; ++qt) acc[ot][qt][v] = bv;
+        }
+    }
+}
+
+// 8 x u16 -> one 16-B fragment, element 0 lowest
+__device__ __forceinline__ cm_u4 cb_pack(const unsigned short (&u)[8]) {
+    return cm_u4{u[0] | ((unsigned)u[1] << 16), u[2] | ((unsigned)u[3] << 16),
+                 u[4] | ((unsigned)u[5] << 16), u[6] | ((unsigned)u[7] << 16)};
+}
+
+// f32 weights W[o0 .. o0+16 NOT-1][c0 .. c0+CC-1][t] -> ws as [c][t][o].  Per output channel
+// the chunk's CC x 7 weights are contiguous: CC * 7 / 4 float4 loads when the chunk is whole and
+// 16-B aligned, scalar loads (0 past C) otherwise.
+template <int CC, int NOT>
+__device__ __forceinline__ void cm_stage_w(float* __restrict__ ws, const float* __restrict__ kern,
+                                           const MfmaGeom& G, int c0, int o0, int tid) {
+    constexpr int CM_O = 16 * NOT, F4 = CC * 7 / 4;
+    for (int e = tid; e < CM_O * F4; e += CM_THREADS) {
+        const int o = e / F4, f = e - o * F4;
+        const int og = o0 + o;
+        float4 v4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        const int64_t base = ((int64_t)og * G.C + c0) * 7 + 4 * f;   // first of 4 (c, t)
+        if (og < G.O) {
+            if (c0 + CC <= G.C && (base & 3) == 0) {
+                v4 = *reinterpret_cast<const float4*>(kern + base);
+            } else {
+                float tmp[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int ct = 4 * f + j, c = c0 + ct / 7;
+                    tmp[j] = c < G.C ? kern[((int64_t)og * G.C + c) * 7 + ct % 7] : 0.f;
+                }
+                v4 = make_float4(tmp[0], tmp[1], tmp[2], tmp[3]);
+            }
+        }
+        const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int ct = 4 * f + j, cc = ct / 7, t = ct - cc * 7;
+            ws[cc * CM_WST + t * CM_O + o] = vv[j];
+        }
+    }
+}
+
+// bf16 weight split: the weights of (output channel og, tap t; t = 7: zeros) for the 8 input
+// channels from c0 as w = h + m + l in bf16, stored as the three fragments of slot (o, t) of a
+// [part][kb][o][g] block with `ostride` channels per (part, kb).  Returns nonzero when some m / l
+// part is (+-0 is zero): when none of a chunk is, the MFMA loop skips parts 2 and 3: half the MFMA
+// work for bf16-exact weights, and an infinite input times a weight then stays +-Inf as in one
+// fp32 product instead of meeting a zero part as Inf * 0 = NaN.
+__device__ __forceinline__ int cb_split_w(const float* __restrict__ kern, int C, int O, int og, int c0,
+                                          int t, cm_u4* __restrict__ dst, int ostride, int o) {
+    unsigned short h[8], m[8], l[8];
+    int ml = 0;
+#pragma unroll
+    for (int cc = 0; cc < 8; ++cc) {
+        const int c = c0 + cc;
+        const float wf = (t < 7 && og < O && c < C) ? kern[((int64_t)og * C + c) * 7 + t] : 0.f;
+        const __bf16 bh = (__bf16)wf;
+        const float r1 = wf - (float)bh;
+        const __bf16 bm = (__bf16)r1;
+        const __bf16 bl = (__bf16)(r1 - (float)bm);
+        h[cc] = __builtin_bit_cast(unsigned short, bh);
+        m[cc] = __builtin_bit_cast(unsigned short, bm);
+        l[cc] = __builtin_bit_cast(unsigned short, bl);
+        ml |= (m[cc] | l[cc]) & 0x7fff;
+    }
+    const int kb = t >> 2, g = t & 3;
+    dst[((0 * 2 + kb) * ostride + o) * 4 + cd_wslot(o, g)] = cb_pack(h);
+    dst[((1 * 2 + kb) * ostride + o) * 4 + cd_wslot(o, g)] = cb_pack(m);
+    dst[((2 * 2 + kb) * ostride + o) * 4 + cd_wslot(o, g)] = cb_pack(l);
+    return ml;
+}
+
+// A workgroup's weight chunk split in the kernel (the register-staged bf16 kernels): thread
+// (o, t) as above into wsb; 3 when the chunk needs all three parts, else 1 (uniform; barrier).
+template <int NOT>
+__device__ __forceinline__ int cb_stage_w(cm_u4* __restrict__ wsb, const float* __restrict__ kern,
+                                          const MfmaGeom& G, int c0, int o0, int tid) {
+    constexpr int CM_O = 16 * NOT;
+    int ml = 0;
+    for (int e = tid; e < CM_O * 8; e += CM_THREADS) {
+        const int o = e >> 3, t = e & 7;
+        ml |= cb_split_w(kern, G.C, G.O, o0 + o, c0, t, wsb, CM_O, o);
+    }
+    return __syncthreads_or(ml != 0) ? 3 : 1;
+}
+
+// bf16 P at stride 1, through registers: rows r0 .. r0+5, columns q0 + mink + (0..71) of the 8
+// channels from c0 as [row][col] fragments (channel innermost), cm_stage_p's padding rules and
+// structural zero column.  216 threads = 72 columns x 3 row phases, two rows each.
+__device__ __forceinline__ void cb_stage_p(cm_u4* __restrict__ psb, const unsigned short* __restrict__ xb,
+                                           const MfmaGeom& G, int c0, int q0, int r0, int tid) {
+    if (tid < 3 * CB_PP) {
+        const unsigned short padv = __builtin_bit_cast(unsigned short, (__bf16)G.pad_value);
+        const int pc = tid % CB_PP, ph = tid / CB_PP;
+        const int px = q0 + G.mink + pc;
+        const bool zc = px >= G.Wp;                      // type1 structural zero column
+        const int64_t xi = zc ? -1 : pad_map(px - G.p, G.w, G.pad_mode);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int pr = ph + 3 * k, py = r0 + pr;
+            const int64_t yi = (!zc && py < G.Hp) ? pad_map(py - G.p, G.h, G.pad_mode) : -1;
+            unsigned short v[8];
+#pragma unroll
+            for (int cc = 0; cc < 8; ++cc) {
+                const int c = c0 + cc;
+                unsigned short e = 0;
+                if (!zc && c < G.C && py < G.Hp)
+                    e = (yi < 0 || xi < 0) ? padv : xb[((int64_t)c * G.h + yi) * G.w + xi];
+                v[cc] = e;
+            }
+            psb[pr * CB_PP + pc] = cb_pack(v);
+        }
+    }
+}
+
+// This lane's P fragment per k block: tap t = 4 kb + lk at its cm_pslot, fragment column li;
+// the 8th tap slot (-1) reads the zero fragment.
+template <int S>
+__device__ __forceinline__ void cb_pidx(int (&pidx)[2], const MfmaGeom& G, int wv, int par, int li, int lk) {
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+        const int t = 4 * kb + lk;
+        pidx[kb] = t < 7 ? cm_pslot<S>(wv, G.dy[t], par ? G.dk[1][t] : G.dk[0][t]) + li : -1;
+    }
+}
 
 // CM_TD epilogue (16-bit outputs): lane (li, lk) holds output channel oc + 16 ot, columns
 // q + 16 qt .. + 3 in its 4 registers: one 8-B store per (ot, qt) when every row's start keeps
@@ -67,6 +288,38 @@ __device__ __forceinline__ void cm_store_cols(const cm_f4 (&acc)[NOT][NQT], Tout
     }
 }
 
+// Epilogue: bias was the accumulator's start; BN / activation (epi_apply); bounds; cast; store.
+// Plain D: one store per register; TD: cm_store_cols.
+template <bool TD, typename Tout, int NOT, int NQT>
+__device__ __forceinline__ void cm_store(const cm_f4 (&acc)[NOT][NQT], Tout* __restrict__ y,
+                                         const MfmaGeom& G, const CmBlock<NOT>& K) {
+    if (K.r >= G.ho) return;
+    Tout* yb = y + K.b * (int64_t)G.O * G.ho * G.wo;
+    if constexpr (TD) {
+        cm_store_cols<Tout, NOT, NQT>(acc, yb, G, K.o0 + K.li, K.q0 + K.lk * 4, K.r);
+        return;
+    }
+#pragma unroll
+    for (int ot = 0; ot < NOT; ++ot)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int o = K.o0 + ot * 16 + K.lk * 4 + v;
+            if (o >= G.O) continue;
+#pragma unroll
+            for (int qt = 0; qt < NQT; ++qt) {
+                const int q = K.q0 + qt * 16 + K.li;
+                if (q >= G.wo) continue;
+                float val = acc[ot][qt][v];
+                if (G.epi.on) val = epi_apply(val, o, G.epi);
+                yb[((int64_t)o * G.ho + K.r) * G.wo + q] = (Tout)val;
+            }
+        }
+}
+
+// ---- the kernels ------------------------------------------------------------------------------
+
+// The parent text, not the shared steps: with them the NOT = 2 instantiations ran 0.5-0.6 % slower
+// (profiles/conv_mfma_refactor_ab.txt)
 template <typename Tin, typename Tout, int NOT>
 __global__ __launch_bounds__(CM_THREADS) void k_hexconv_mfma(const Tin* __restrict__ x,
                                                                 const float* __restrict__ kern,
@@ -182,160 +435,52 @@ __global__ __launch_bounds__(CM_THREADS) void k_hexconv_mfma(const Tin* __restri
         }
 }
 
-typedef __bf16 cm_b8 __attribute__((ext_vector_type(8)));
-typedef unsigned cm_u4 __attribute__((ext_vector_type(4)));
-// The bf16 kernels' weight-fragment LDS layout: channel o's four k-group fragments (16 B each)
-// in a rotated order, so each of ds_read_b128's four 16-lane groups ({0-3,12-15,20-27},
-// {4-11,16-19,28-31}, and the same + 32: MI355X_MICROARCH.md section LDS) reads 16 distinct
-// 16-B bank slots; the plain order o * 4 + g put lanes li and li + 12 (and li + 4, li + 8) of a
-// group on one slot (2-way conflicts; r04 session O counters: 39 % of the LDS cycles).
-__host__ __device__ constexpr int cd_wslot(int o, int g) { return (g + 2 * ((o & 15) >> 2)) & 3; }
-
-constexpr int CB_PP = 72;                   // staged columns (as CM_PP)
-constexpr int CB_PSZ = CM_PR * CB_PP + 1;   // P fragments per chunk (+1: the zero fragment)
-
+// bf16 inputs, register staging (the DMA kernel's fallback: odd widths, unaligned sources,
+// HYGRID_CONV_DMA=0, and its reference in the tests).  P chunk: [row][col] fragments of the 8
+// channels (16 B each, channel innermost); weights: [part][kb][o][g] fragments of the 8 channels
+// of tap 4 kb + g.  Plain D only (TD = false).
 template <typename Tout, int NOT>
 __global__ __launch_bounds__(CM_THREADS) void k_hexconv_mfma_bf16(const __bf16* __restrict__ x,
                                                                   const float* __restrict__ kern,
                                                                   const float* __restrict__ bias,
                                                                   Tout* __restrict__ y, MfmaGeom G) {
-    constexpr int CM_O = 16 * NOT;                       // output channels of this workgroup
-    // P chunk: [row][col] fragments of the 8 channels (16 B each, channel innermost);
-    // weights: [part][kb][o][g] fragments of the 8 channels of tap 4 kb + g
     __shared__ cm_u4 psb[CB_PSZ];
-    __shared__ cm_u4 wsb[3 * 2 * CM_O * 4];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    unsigned bid = xcd_swizzle(blockIdx.x, gridDim.x);
-    const int tq = (int)(bid % G.ntq); bid /= G.ntq;
-    const int tr = (int)(bid % G.ntr); bid /= G.ntr;
-    const int to = (int)(bid % G.nto);
-    const int64_t b = bid / G.nto;
-    const int q0 = tq * CM_Q, r0 = tr * CM_ROWS, o0 = to * CM_O;
-    const int r = r0 + wv;
-    const int par = r & 1;
-    const int Wp = G.w + 2 * G.p, Hp = G.h + 2 * G.p;
-    const int li = lane & 15, lg = lane >> 4;            // fragment row / column, k group
-    const unsigned short padv = __builtin_bit_cast(unsigned short, (__bf16)G.pad_value);
-
-    cm_f4 acc[NOT][4];
-#pragma unroll
-    for (int ot = 0; ot < NOT; ++ot) {
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int o = o0 + ot * 16 + lg * 4 + v;
-            const float bv = (bias && o < G.O) ? bias[o] : 0.f;
-#pragma unroll
-            for (int qt = 0; qt < 4; ++qt) acc[ot][qt][v] = bv;
-        }
-    }
-    if (tid == 0) psb[CB_PSZ - 1] = cm_u4{0u, 0u, 0u, 0u};
-    // this lane's P fragment (per k block and column tile): tap t = 4 kb + lg, row wv + dy_t,
-    // column qt * 16 + li + dk_t; the 8th tap slot reads the zero fragment
+    __shared__ cm_u4 wsb[3 * 2 * 16 * NOT * 4];
+    const CmBlock<NOT> K(G);
+    cm_f4 acc[NOT][CM_NQT];
+    cm_bias_init<false>(acc, bias, G, K.o0, K.li, K.lk);
+    if (K.tid == 0) psb[CB_PSZ - 1] = cm_u4{0u, 0u, 0u, 0u};
     int pidx[2];
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-        const int t = 4 * kb + lg;
-        pidx[kb] = t < 7 ? (wv + G.dy[t]) * CB_PP + li + (par ? G.dk[1][t] : G.dk[0][t]) : -1;
-    }
+    cb_pidx<1>(pidx, G, K.wv, K.par, K.li, K.lk);
 
-    const unsigned short* xb = reinterpret_cast<const unsigned short*>(x) + b * (int64_t)G.C * G.h * G.w;
+    const unsigned short* xb = reinterpret_cast<const unsigned short*>(x) + K.b * (int64_t)G.C * G.h * G.w;
     for (int c0 = 0; c0 < G.C; c0 += CM_CC) {
-        // ---- stage P rows r0 .. r0+5, columns q0 + mink + (0..71), 8 channels ------------
-        if (tid < 3 * CB_PP) {
-            const int pc = tid % CB_PP, ph = tid / CB_PP;
-            const int px = q0 + G.mink + pc;
-            const bool zc = px >= Wp;                        // type1 structural zero column
-            const int64_t xi = zc ? -1 : pad_map(px - G.p, G.w, G.pad_mode);
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const int pr = ph + 3 * k, py = r0 + pr;
-                const int64_t yi = (!zc && py < Hp) ? pad_map(py - G.p, G.h, G.pad_mode) : -1;
-                unsigned short v[8];
-#pragma unroll
-                for (int cc = 0; cc < 8; ++cc) {
-                    const int c = c0 + cc;
-                    unsigned short e = 0;
-                    if (!zc && c < G.C && py < Hp)
-                        e = (yi < 0 || xi < 0) ? padv : xb[((int64_t)c * G.h + yi) * G.w + xi];
-                    v[cc] = e;
-                }
-                psb[pr * CB_PP + pc] = cm_u4{v[0] | ((unsigned)v[1] << 16), v[2] | ((unsigned)v[3] << 16),
-                                             v[4] | ((unsigned)v[5] << 16), v[6] | ((unsigned)v[7] << 16)};
-            }
-        }
-        // ---- stage the weights of taps (o, t), 8 channels, as 3 bf16 parts ----------------
-        // (ml: some weight of the chunk needs its second / third part; when none does, the
-        // pt = 1, 2 passes are skipped: half the MFMA work for bf16-exact weights, and an
-        // infinite input times a weight then stays +-Inf as in one fp32 product instead of
-        // meeting a zero part as Inf * 0 = NaN)
-        int ml = 0;
-        for (int e = tid; e < CM_O * 8; e += CM_THREADS) {
-            const int o = e >> 3, t = e & 7, og = o0 + o;
-            unsigned short h[8], m[8], l[8];
-#pragma unroll
-            for (int cc = 0; cc < 8; ++cc) {
-                const int c = c0 + cc;
-                const float wf = (t < 7 && og < G.O && c < G.C) ? kern[((int64_t)og * G.C + c) * 7 + t] : 0.f;
-                const __bf16 bh = (__bf16)wf;
-                const float r1 = wf - (float)bh;
-                const __bf16 bm = (__bf16)r1;
-                const __bf16 bl = (__bf16)(r1 - (float)bm);
-                h[cc] = __builtin_bit_cast(unsigned short, bh);
-                m[cc] = __builtin_bit_cast(unsigned short, bm);
-                l[cc] = __builtin_bit_cast(unsigned short, bl);
-                ml |= (m[cc] | l[cc]) & 0x7fff;              // a nonzero part (+-0 is zero)
-            }
-            const int kb = t >> 2, g = t & 3;
-            auto pk = [](const unsigned short* u) {
-                return cm_u4{u[0] | ((unsigned)u[1] << 16), u[2] | ((unsigned)u[3] << 16),
-                             u[4] | ((unsigned)u[5] << 16), u[6] | ((unsigned)u[7] << 16)};
-            };
-            wsb[((0 * 2 + kb) * CM_O + o) * 4 + cd_wslot(o, g)] = pk(h);
-            wsb[((1 * 2 + kb) * CM_O + o) * 4 + cd_wslot(o, g)] = pk(m);
-            wsb[((2 * 2 + kb) * CM_O + o) * 4 + cd_wslot(o, g)] = pk(l);
-        }
-        const int nparts = __syncthreads_or(ml != 0) ? 3 : 1;   // uniform per workgroup
-        // ---- 2 k blocks x 4 column tiles x 3 weight parts x NOT channel tiles -------------
+        cb_stage_p(psb, xb, G, c0, K.q0, K.r0, K.tid);
+        const int nparts = cb_stage_w<NOT>(wsb, kern, G, c0, K.o0, K.tid);   // barrier inside
+        // ---- 2 k blocks x 4 column tiles x nparts weight parts x NOT channel tiles ---------
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
-            cm_b8 bf[4];
+            cm_b8 bf[CM_NQT];
 #pragma unroll
-            for (int qt = 0; qt < 4; ++qt)
+            for (int qt = 0; qt < CM_NQT; ++qt)
                 bf[qt] = __builtin_bit_cast(cm_b8, psb[pidx[kb] < 0 ? CB_PSZ - 1 : pidx[kb] + qt * 16]);
 #pragma unroll
             for (int pt = 0; pt < 3; ++pt) {
                 if (pt >= nparts) break;
 #pragma unroll
                 for (int ot = 0; ot < NOT; ++ot) {
-                    const cm_b8 af = __builtin_bit_cast(cm_b8, wsb[((pt * 2 + kb) * CM_O + ot * 16 + li) * 4 + cd_wslot(li, lg)]);
+                    const cm_b8 af = __builtin_bit_cast(cm_b8, wsb[((pt * 2 + kb) * (16 * NOT) + ot * 16 + K.li) * 4 + cd_wslot(K.li, K.lk)]);
 #pragma unroll
-                    for (int qt = 0; qt < 4; ++qt)
+                    for (int qt = 0; qt < CM_NQT; ++qt)
                         acc[ot][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf[qt], acc[ot][qt], 0, 0, 0);
                 }
             }
         }
         __syncthreads();
     }
-
-    if (r >= G.ho) return;
-    Tout* yb = y + b * (int64_t)G.O * G.ho * G.wo;
-#pragma unroll
-    for (int ot = 0; ot < NOT; ++ot)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int o = o0 + ot * 16 + lg * 4 + v;
-            if (o >= G.O) continue;
-#pragma unroll
-            for (int qt = 0; qt < 4; ++qt) {
-                const int q = q0 + qt * 16 + li;
-                if (q >= G.wo) continue;
-                float val = acc[ot][qt][v];
-                if (G.epi.on) val = epi_apply(val, o, G.epi);
-                yb[((int64_t)o * G.ho + r) * G.wo + q] = (Tout)val;
-            }
-        }
+    cm_store<false>(acc, y, G, K);
 }
+
 
 // ---- bf16 inputs, staging by LDS-DMA (round 4) -------------------------------------------
 // The same GEMM and fragment maps as k_hexconv_mfma_bf16, with the staging taken off the
@@ -358,30 +503,7 @@ __global__ __launch_bounds__(128) void k_wsplit_bf16(const float* __restrict__ k
                                                      int* __restrict__ flag, int C, int O, int Opad) {
     const int ci = blockIdx.x, ob = blockIdx.y;
     const int o = ob * 16 + (threadIdx.x >> 3), t = threadIdx.x & 7;
-    unsigned short h[8], m[8], l[8];
-    int ml = 0;
-#pragma unroll
-    for (int cc = 0; cc < 8; ++cc) {
-        const int c = ci * 8 + cc;
-        const float wv = (t < 7 && o < O && c < C) ? kern[((int64_t)o * C + c) * 7 + t] : 0.f;
-        const __bf16 bh = (__bf16)wv;
-        const float r1 = wv - (float)bh;
-        const __bf16 bm = (__bf16)r1;
-        const __bf16 bl = (__bf16)(r1 - (float)bm);
-        h[cc] = __builtin_bit_cast(unsigned short, bh);
-        m[cc] = __builtin_bit_cast(unsigned short, bm);
-        l[cc] = __builtin_bit_cast(unsigned short, bl);
-        ml |= (m[cc] | l[cc]) & 0x7fff;
-    }
-    auto pk = [](const unsigned short* u) {
-        return cm_u4{u[0] | ((unsigned)u[1] << 16), u[2] | ((unsigned)u[3] << 16),
-                     u[4] | ((unsigned)u[5] << 16), u[6] | ((unsigned)u[7] << 16)};
-    };
-    const int kb = t >> 2, g = t & 3;
-    auto at = [&](int pt) { return ((((int64_t)ci * 3 + pt) * 2 + kb) * Opad + o) * 4 + cd_wslot(o, g); };
-    wf[at(0)] = pk(h);
-    wf[at(1)] = pk(m);
-    wf[at(2)] = pk(l);
+    const int ml = cb_split_w(kern, C, O, o, ci * 8, t, wf + (int64_t)ci * 6 * Opad * 4, Opad, o);
     const int any = __syncthreads_or(ml != 0);
     if (threadIdx.x == 0) flag[ci * (Opad / 16) + ob] = any;
 }
@@ -397,6 +519,8 @@ __device__ __forceinline__ void cd_wait_vm() {
 // MFMAs cover each other's waits; double-buffered, 71 KB and 2 workgroups per CU, was 18 %
 // slower, and 3 column tiles with one raw-P buffer for a 4th wave per SIMD 4 % slower: both
 // removed in round 6).  The raw P rows are double-buffered.
+// (its own text, not the shared steps: with them it ran 0.7-1.3 % slower on 32 -> 32 and 64 -> 64,
+// profiles/conv_mfma_refactor_ab.txt)
 template <typename Tout, int NOT>
 __global__ __launch_bounds__(CM_THREADS) __attribute__((amdgpu_waves_per_eu(1)))
 void k_hexconv_mfma_bf16d(const __bf16* __restrict__ x,
@@ -630,23 +754,6 @@ void k_hexconv_mfma_bf16d(const __bf16* __restrict__ x,
 // 16 consecutive LDS slots of plane dk & 1 starting at slot (dk >> 1) + li, and the fragment
 // maps, the weight layouts, the accumulators and the epilogues are the stride-1 kernels'.
 // Sibling kernels, not a stride template argument: the stride-1 kernels keep their symbols.
-//
-// Input channels per LDS chunk of k_hexconv_mfma_s2: 4 (20.7 KB of P + 7.4 KB of weights = 28.2 KB,
-// 3-4 waves per SIMD) against 8 (56.3 KB, 2 workgroups per CU): 4.55 against 5.90 ms on
-// 64 -> 128 1080p b4 f32, 0.264 / 0.397 ms on the 3 -> 64 stem, 0.230 / 0.346 ms on 16 -> 16
-// 540p b8, 2.40 / 3.07 ms on 128 -> 256 540p b2 (profiles/conv_mfma_stride2_ab.txt): as at
-// stride 1, occupancy, not barrier count, is what the staging latency needs.
-#ifndef CS_CC
-#define CS_CC 4
-#endif
-static_assert(CS_CC % 4 == 0 && CS_CC <= CM_CC, "chunk: whole MFMA k quads, the weight stride's rows");
-#ifndef CS_PLANES
-#define CS_PLANES 1                          // 0 (A/B build): k_hexconv_mfma_s2 keeps a staged row's
-#endif                                       // columns in their natural order, stride-2 B reads
-
-__device__ __forceinline__ int cs_slot(int row, int dk) {     // staged (row, column 2 q' + dk) at q' = 0
-    return row * CS_PP + (dk & 1) * CS_PL + (dk >> 1);
-}
 
 // Stage P rows 2 r0 .. 2 r0 + 8 (staged frame), columns 2 q0 + mink + (0..129), of channels
 // c0 .. c0+CS_CC-1 as fp32 [c][row][plane][slot].  195 threads = 65 slots x 3 row phases; a
@@ -672,9 +779,9 @@ __device__ __forceinline__ void cs_stage_p(float* __restrict__ ps, const Tin* __
                 if (!z0) v0 = (yi < 0 || x0 < 0) ? G.pad_value : (float)xb[row + x0];
                 if (!z1) v1 = (yi < 0 || x1 < 0) ? G.pad_value : (float)xb[row + x1];
             }
-            float* const d = ps + cc * CS_CST + pr * CS_PP + (CS_PLANES ? sl : 2 * sl);
+            float* const d = ps + cc * CS_CST + pr * CS_PP + sl;
             d[0] = v0;
-            d[CS_PLANES ? CS_PL : 1] = v1;
+            d[CS_PL] = v1;
         }
     }
 }
@@ -686,111 +793,41 @@ __global__ __launch_bounds__(CM_THREADS) void k_hexconv_mfma_s2(const Tin* __res
                                                                    Tout* __restrict__ y, MfmaGeom G) {
     __shared__ float ps[CS_CC * CS_CST];                 // P chunk [c][row][plane][slot]
     __shared__ float ws[CS_CC * CM_WST];                 // weight chunk [c][t][o]
-    constexpr int CM_O = 16 * NOT;                       // output channels of this workgroup
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    unsigned bid = xcd_swizzle(blockIdx.x, gridDim.x);
-    const int tq = (int)(bid % G.ntq); bid /= G.ntq;
-    const int tr = (int)(bid % G.ntr); bid /= G.ntr;
-    const int to = (int)(bid % G.nto);
-    const int64_t b = bid / G.nto;
-    const int q0 = tq * CM_Q, r0 = tr * CM_ROWS, o0 = to * (16 * NOT);
-    const int r = r0 + wv;                               // this wave's output row
-    const int par = r & 1;
-    const int li = lane & 15, lk = lane >> 4;            // fragment row / k of this lane
+    constexpr bool TD = cm_td<Tout>;
+    const CmBlock<NOT> K(G);
+    cm_f4 acc[NOT][CM_NQT];
+    cm_bias_init<TD>(acc, bias, G, K.o0, K.li, K.lk);
 
-    constexpr bool TD = CM_TD && sizeof(Tout) == 2;      // 16-bit outputs: D as [column][channel]
-    cm_f4 acc[NOT][4];
-#pragma unroll
-    for (int ot = 0; ot < NOT; ++ot) {
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int o = o0 + ot * 16 + (TD ? li : lk * 4 + v);
-            const float bv = (bias && o < G.O) ? bias[o] : 0.f;
-#pragma unroll
-            for (int qt = 0; qt < 4; ++qt) acc[ot][qt][v] = bv;
-        }
-    }
-
-    const Tin* xb = x + b * (int64_t)G.C * G.h * G.w;
+    const Tin* xb = x + K.b * (int64_t)G.C * G.h * G.w;
     for (int c0 = 0; c0 < G.C; c0 += CS_CC) {
-        cs_stage_p(ps, xb, G, c0, q0, r0, tid);
-        // ---- stage weights W[o0 .. o0+CM_O-1][c0 .. c0+CS_CC-1][t] as [c][t][o] (k_hexconv_mfma's)
-        for (int e = tid; e < CM_O * (CS_CC * 7 / 4); e += CM_THREADS) {
-            const int o = e / (CS_CC * 7 / 4), f = e - o * (CS_CC * 7 / 4);
-            const int og = o0 + o;
-            float4 v4 = make_float4(0.f, 0.f, 0.f, 0.f);
-            const int64_t base = ((int64_t)og * G.C + c0) * 7 + 4 * f;   // first of 4 (c, t)
-            if (og < G.O) {
-                if (c0 + CS_CC <= G.C && (base & 3) == 0) {
-                    v4 = *reinterpret_cast<const float4*>(kern + base);
-                } else {
-                    float tmp[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int ct = 4 * f + j, c = c0 + ct / 7;
-                        tmp[j] = c < G.C ? kern[((int64_t)og * G.C + c) * 7 + ct % 7] : 0.f;
-                    }
-                    v4 = make_float4(tmp[0], tmp[1], tmp[2], tmp[3]);
-                }
-            }
-            const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int ct = 4 * f + j, cc = ct / 7, t = ct - cc * 7;
-                ws[cc * CM_WST + t * CM_O + o] = vv[j];
-            }
-        }
+        cs_stage_p(ps, xb, G, c0, K.q0, K.r0, K.tid);
+        cm_stage_w<CS_CC, NOT>(ws, kern, G, c0, K.o0, K.tid);
         __syncthreads();
-        // ---- 7 taps x CS_CC / 4 channel quads x (NOT x 4) MFMAs -------------------------
+        // ---- 7 taps x CS_CC / 4 channel quads x (NOT x 4) MFMAs ---------------------------
 #pragma unroll
         for (int t = 0; t < 7; ++t) {
-            const int dk = par ? G.dk[1][t] : G.dk[0][t];
-            const float* pb = CS_PLANES ? ps + lk * CS_CST + cs_slot(2 * wv + G.dy[t], dk) + li
-                                        : ps + lk * CS_CST + (2 * wv + G.dy[t]) * CS_PP + dk + 2 * li;
-            const float* wb = ws + lk * CM_WST + t * CM_O + li;
+            const int dk = K.par ? G.dk[1][t] : G.dk[0][t];
+            const float* pb = ps + K.lk * CS_CST + cm_pslot<2>(K.wv, G.dy[t], dk) + K.li;
+            const float* wb = ws + K.lk * CM_WST + t * (16 * NOT) + K.li;
 #pragma unroll
             for (int cq = 0; cq < CS_CC / 4; ++cq) {
-                float af[NOT], bf[4];
+                float af[NOT], bf[CM_NQT];
 #pragma unroll
                 for (int ot = 0; ot < NOT; ++ot) af[ot] = wb[cq * 4 * CM_WST + ot * 16];
 #pragma unroll
-                for (int qt = 0; qt < 4; ++qt) bf[qt] = pb[cq * 4 * CS_CST + qt * (CS_PLANES ? 16 : 32)];
+                for (int qt = 0; qt < CM_NQT; ++qt) bf[qt] = pb[cq * 4 * CS_CST + qt * 16];
 #pragma unroll
                 for (int ot = 0; ot < NOT; ++ot)
 #pragma unroll
-                    for (int qt = 0; qt < 4; ++qt)
+                    for (int qt = 0; qt < CM_NQT; ++qt)
                         acc[ot][qt] = TD ? __builtin_amdgcn_mfma_f32_16x16x4f32(bf[qt], af[ot], acc[ot][qt], 0, 0, 0)
                                             : __builtin_amdgcn_mfma_f32_16x16x4f32(af[ot], bf[qt], acc[ot][qt], 0, 0, 0);
             }
         }
         __syncthreads();
     }
-
-    if (r >= G.ho) return;
-    Tout* yb = y + b * (int64_t)G.O * G.ho * G.wo;
-    if constexpr (TD) {
-        cm_store_cols<Tout, NOT, 4>(acc, yb, G, o0 + li, q0 + lk * 4, r);
-        return;
-    }
-#pragma unroll
-    for (int ot = 0; ot < NOT; ++ot)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int o = o0 + ot * 16 + lk * 4 + v;
-            if (o >= G.O) continue;
-#pragma unroll
-            for (int qt = 0; qt < 4; ++qt) {
-                const int q = q0 + qt * 16 + li;
-                if (q >= G.wo) continue;
-                float val = acc[ot][qt][v];
-                if (G.epi.on) val = epi_apply(val, o, G.epi);
-                yb[((int64_t)o * G.ho + r) * G.wo + q] = (Tout)val;
-            }
-        }
+    cm_store<TD>(acc, y, G, K);
 }
-
-constexpr int CSB_PSZ = CS_PR * CS_PP + 1;   // bf16 P fragments per chunk (+1: the zero fragment)
 
 // k_hexconv_mfma_bf16 at stride 2: register-staged P fragments [row][plane][slot] of the 8
 // channels, the same weight split and fragment layout.
@@ -799,46 +836,21 @@ __global__ __launch_bounds__(CM_THREADS) void k_hexconv_mfma_bf16_s2(const __bf1
                                                                      const float* __restrict__ kern,
                                                                      const float* __restrict__ bias,
                                                                      Tout* __restrict__ y, MfmaGeom G) {
-    constexpr int CM_O = 16 * NOT;
     __shared__ cm_u4 psb[CSB_PSZ];
-    __shared__ cm_u4 wsb[3 * 2 * CM_O * 4];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    unsigned bid = xcd_swizzle(blockIdx.x, gridDim.x);
-    const int tq = (int)(bid % G.ntq); bid /= G.ntq;
-    const int tr = (int)(bid % G.ntr); bid /= G.ntr;
-    const int to = (int)(bid % G.nto);
-    const int64_t b = bid / G.nto;
-    const int q0 = tq * CM_Q, r0 = tr * CM_ROWS, o0 = to * CM_O;
-    const int r = r0 + wv;
-    const int par = r & 1;
+    __shared__ cm_u4 wsb[3 * 2 * 16 * NOT * 4];
+    const CmBlock<NOT> K(G);
+    const int tid = K.tid, q0 = K.q0, r0 = K.r0, o0 = K.o0;
     const int Wp = G.w + 2 * G.p, Hp = G.h + 2 * G.p;
-    const int li = lane & 15, lg = lane >> 4;            // fragment row / column, k group
     const unsigned short padv = __builtin_bit_cast(unsigned short, (__bf16)G.pad_value);
 
-    constexpr bool TD = CM_TD && sizeof(Tout) == 2;      // 16-bit outputs: D as [column][channel]
-    cm_f4 acc[NOT][4];
-#pragma unroll
-    for (int ot = 0; ot < NOT; ++ot) {
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int o = o0 + ot * 16 + (TD ? li : lg * 4 + v);
-            const float bv = (bias && o < G.O) ? bias[o] : 0.f;
-#pragma unroll
-            for (int qt = 0; qt < 4; ++qt) acc[ot][qt][v] = bv;
-        }
-    }
+    constexpr bool TD = cm_td<Tout>;
+    cm_f4 acc[NOT][CM_NQT];
+    cm_bias_init<TD>(acc, bias, G, o0, K.li, K.lk);
     if (tid == 0) psb[CSB_PSZ - 1] = cm_u4{0u, 0u, 0u, 0u};
-    // this lane's P fragment (per k block and column tile): tap t = 4 kb + lg, staged row
-    // 2 wv + dy_t, column 2 (qt * 16 + li) + dk_t; the 8th tap slot reads the zero fragment
     int pidx[2];
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-        const int t = 4 * kb + lg;
-        pidx[kb] = t < 7 ? cs_slot(2 * wv + G.dy[t], par ? G.dk[1][t] : G.dk[0][t]) + li : -1;
-    }
+    cb_pidx<2>(pidx, G, K.wv, K.par, K.li, K.lk);
 
-    const unsigned short* xb = reinterpret_cast<const unsigned short*>(x) + b * (int64_t)G.C * G.h * G.w;
+    const unsigned short* xb = reinterpret_cast<const unsigned short*>(x) + K.b * (int64_t)G.C * G.h * G.w;
     for (int c0 = 0; c0 < G.C; c0 += CM_CC) {
         // ---- stage P rows 2 r0 .. 2 r0+8, columns 2 q0 + mink + (0..129), 8 channels -----
         // 195 threads = 65 slots x 3 row phases; a thread's two columns are its slot's planes
@@ -864,55 +876,26 @@ __global__ __launch_bounds__(CM_THREADS) void k_hexconv_mfma_bf16_s2(const __bf1
                             e = (yi < 0 || xi[pl] < 0) ? padv : xb[((int64_t)c * G.h + yi) * G.w + xi[pl]];
                         v[cc] = e;
                     }
-                    psb[pr * CS_PP + pl * CS_PL + sl] =
-                        cm_u4{v[0] | ((unsigned)v[1] << 16), v[2] | ((unsigned)v[3] << 16),
-                              v[4] | ((unsigned)v[5] << 16), v[6] | ((unsigned)v[7] << 16)};
+                    psb[pr * CS_PP + pl * CS_PL + sl] = cb_pack(v);
                 }
             }
         }
-        // ---- stage the weights of taps (o, t), 8 channels, as 3 bf16 parts (k_hexconv_mfma_bf16's)
-        int ml = 0;
-        for (int e = tid; e < CM_O * 8; e += CM_THREADS) {
-            const int o = e >> 3, t = e & 7, og = o0 + o;
-            unsigned short h[8], m[8], l[8];
-#pragma unroll
-            for (int cc = 0; cc < 8; ++cc) {
-                const int c = c0 + cc;
-                const float wf = (t < 7 && og < G.O && c < G.C) ? kern[((int64_t)og * G.C + c) * 7 + t] : 0.f;
-                const __bf16 bh = (__bf16)wf;
-                const float r1 = wf - (float)bh;
-                const __bf16 bm = (__bf16)r1;
-                const __bf16 bl = (__bf16)(r1 - (float)bm);
-                h[cc] = __builtin_bit_cast(unsigned short, bh);
-                m[cc] = __builtin_bit_cast(unsigned short, bm);
-                l[cc] = __builtin_bit_cast(unsigned short, bl);
-                ml |= (m[cc] | l[cc]) & 0x7fff;              // a nonzero part (+-0 is zero)
-            }
-            const int kb = t >> 2, g = t & 3;
-            auto pk = [](const unsigned short* u) {
-                return cm_u4{u[0] | ((unsigned)u[1] << 16), u[2] | ((unsigned)u[3] << 16),
-                             u[4] | ((unsigned)u[5] << 16), u[6] | ((unsigned)u[7] << 16)};
-            };
-            wsb[((0 * 2 + kb) * CM_O + o) * 4 + cd_wslot(o, g)] = pk(h);
-            wsb[((1 * 2 + kb) * CM_O + o) * 4 + cd_wslot(o, g)] = pk(m);
-            wsb[((2 * 2 + kb) * CM_O + o) * 4 + cd_wslot(o, g)] = pk(l);
-        }
-        const int nparts = __syncthreads_or(ml != 0) ? 3 : 1;   // uniform per workgroup
-        // ---- 2 k blocks x 4 column tiles x 3 weight parts x NOT channel tiles -------------
+        const int nparts = cb_stage_w<NOT>(wsb, kern, G, c0, o0, tid);   // barrier inside
+        // ---- 2 k blocks x 4 column tiles x nparts weight parts x NOT channel tiles ---------
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
-            cm_b8 bf[4];
+            cm_b8 bf[CM_NQT];
 #pragma unroll
-            for (int qt = 0; qt < 4; ++qt)
+            for (int qt = 0; qt < CM_NQT; ++qt)
                 bf[qt] = __builtin_bit_cast(cm_b8, psb[pidx[kb] < 0 ? CSB_PSZ - 1 : pidx[kb] + qt * 16]);
 #pragma unroll
             for (int pt = 0; pt < 3; ++pt) {
                 if (pt >= nparts) break;
 #pragma unroll
                 for (int ot = 0; ot < NOT; ++ot) {
-                    const cm_b8 af = __builtin_bit_cast(cm_b8, wsb[((pt * 2 + kb) * CM_O + ot * 16 + li) * 4 + cd_wslot(li, lg)]);
+                    const cm_b8 af = __builtin_bit_cast(cm_b8, wsb[((pt * 2 + kb) * (16 * NOT) + ot * 16 + K.li) * 4 + cd_wslot(K.li, K.lk)]);
 #pragma unroll
-                    for (int qt = 0; qt < 4; ++qt)
+                    for (int qt = 0; qt < CM_NQT; ++qt)
                         acc[ot][qt] = TD ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[qt], af, acc[ot][qt], 0, 0, 0)
                                             : __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf[qt], acc[ot][qt], 0, 0, 0);
                 }
@@ -921,27 +904,7 @@ __global__ __launch_bounds__(CM_THREADS) void k_hexconv_mfma_bf16_s2(const __bf1
         __syncthreads();
     }
 
-    if (r >= G.ho) return;
-    Tout* yb = y + b * (int64_t)G.O * G.ho * G.wo;
-    if constexpr (TD) {
-        cm_store_cols<Tout, NOT, 4>(acc, yb, G, o0 + li, q0 + lg * 4, r);
-        return;
-    }
-#pragma unroll
-    for (int ot = 0; ot < NOT; ++ot)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int o = o0 + ot * 16 + lg * 4 + v;
-            if (o >= G.O) continue;
-#pragma unroll
-            for (int qt = 0; qt < 4; ++qt) {
-                const int q = q0 + qt * 16 + li;
-                if (q >= G.wo) continue;
-                float val = acc[ot][qt][v];
-                if (G.epi.on) val = epi_apply(val, o, G.epi);
-                yb[((int64_t)o * G.ho + r) * G.wo + q] = (Tout)val;
-            }
-        }
+    cm_store<TD>(acc, y, G, K);
 }
 
 // Output-channel tiles per workgroup (A/B switch HYGRID_CONV_NT=2: two for any O)
@@ -955,9 +918,12 @@ constexpr int CS_MIN_O = 16;                 // stride 2: out_channels from whic
 // chunk padded with zeros (staging and weights read 0 past C): HexConv2d(3 -> 64) 1080p b4
 // 2.76 -> 0.50 ms (bf16) and 2.84 -> 1.02 ms (f32) against the generic kernel at stride 1,
 // round 6, profiles/r06/stem_conv_ab.txt; stride 2: profiles/conv_mfma_stride2_ab.txt.
-int conv_fwd_route(int x_dtype, int w_dtype, int y_dtype, int64_t B, int64_t C, int64_t O,
-                   int64_t h, int64_t w, int radius, int stride, int padding, int dilation,
-                   int groups, int off, int pad_mode, double pad_value, unsigned x_align) {
+// G, nt: the complete geometry (nto included, epilogue off) and the output-channel tiles per
+// workgroup of the kernel named, for the launch.
+static int fwd_route(int x_dtype, int w_dtype, int y_dtype, int64_t B, int64_t C, int64_t O,
+                     int64_t h, int64_t w, int radius, int stride, int padding, int dilation,
+                     int groups, int off, int pad_mode, double pad_value, unsigned x_align,
+                     MfmaGeom& G, int& nt) {
     if (env_is("HYGRID_CONV_MFMA", "0")) return HG_CONV_FWD_OTHER;   // A/B switch: generic kernels
     if (w_dtype != HG_F32) return HG_CONV_FWD_OTHER;
     if (radius != 2 || (stride != 1 && stride != 2) || dilation != 1 || groups != 1)
@@ -965,11 +931,12 @@ int conv_fwd_route(int x_dtype, int w_dtype, int y_dtype, int64_t B, int64_t C, 
     if (C < 1 || O < (stride == 2 ? CS_MIN_O : 16) || padding < 0 || padding > 2)
         return HG_CONV_FWD_OTHER;
     if (!conv_mfma_size_ok(C, O, h, w)) return HG_CONV_FWD_OTHER;   // 32-bit buffer offsets
-    MfmaGeom G = {};
+    G = {};
     if (!conv_mfma_forward_geom(G, B, C, O, h, w, padding, off, pad_mode, pad_value, stride))
         return HG_CONV_FWD_OTHER;
-    const int nt = conv_mfma_nt(O);
-    const int64_t blocks = B * (int64_t)G.ntq * G.ntr * ((G.O + 16 * nt - 1) / (16 * nt));
+    nt = conv_mfma_nt(O);
+    G.nto = (G.O + 16 * nt - 1) / (16 * nt);
+    const int64_t blocks = B * (int64_t)G.ntq * G.ntr * G.nto;
     if (blocks > INT_MAX || blocks <= 0) return HG_CONV_FWD_OTHER;
     // bf16 inputs: the split-weight bf16 kernel, when the pad value is a bf16 (the padded
     // input keeps the input's dtype, as F.pad does; anything else keeps the f32 kernel)
@@ -990,92 +957,98 @@ int conv_fwd_route(int x_dtype, int w_dtype, int y_dtype, int64_t B, int64_t C, 
     return pair ? HG_CONV_FWD_MFMA_F32 : HG_CONV_FWD_OTHER;
 }
 
+int conv_fwd_route(int x_dtype, int w_dtype, int y_dtype, int64_t B, int64_t C, int64_t O,
+                   int64_t h, int64_t w, int radius, int stride, int padding, int dilation,
+                   int groups, int off, int pad_mode, double pad_value, unsigned x_align) {
+    MfmaGeom G;
+    int nt;
+    return fwd_route(x_dtype, w_dtype, y_dtype, B, C, O, h, w, radius, stride, padding, dilation,
+                     groups, off, pad_mode, pad_value, x_align, G, nt);
+}
+
+// One launch of a kernel instantiated for NOT = 2 and 4: launch(integral_constant<int, NOT>)
+template <typename F>
+static int launch_nt(int nt, F&& launch) {
+    if (nt == 2) launch(std::integral_constant<int, 2>{});
+    else launch(std::integral_constant<int, 4>{});
+    return launch_status();
+}
+
+template <typename Tout>
+static int launch_bf16(int route, const void* x, const float* k, const float* b, void* y,
+                       const MfmaGeom& G, int nt, int stride, hipStream_t st) {
+    const dim3 grid((unsigned)(G.B * G.ntq * G.ntr * G.nto)), blk(CM_THREADS);
+    const __bf16* xx = static_cast<const __bf16*>(x);
+    Tout* yy = static_cast<Tout*>(y);
+    if (route == HG_CONV_FWD_MFMA_BF16)
+        return launch_nt(nt, [&](auto n) {
+            auto kn = stride == 2 ? k_hexconv_mfma_bf16_s2<Tout, n()> : k_hexconv_mfma_bf16<Tout, n()>;
+            hipLaunchKernelGGL(kn, grid, blk, 0, st, xx, k, b, yy, G);
+        });
+    // LDS-DMA: the weight parts and their flags, split once into stream-ordered scratch
+    const int nch = (G.C + CM_CC - 1) / CM_CC, Opad = G.nto * 16 * nt;
+    const size_t wbytes = (size_t)nch * 6 * Opad * 64, fbytes = (size_t)nch * (Opad / 16) * 4;
+    void* ws = nullptr;
+    hipError_t e = hipMallocAsync(&ws, wbytes + fbytes, st);
+    if (e != hipSuccess) return (int)e;
+    cm_u4* wfr = static_cast<cm_u4*>(ws);
+    int* flg = reinterpret_cast<int*>(static_cast<char*>(ws) + wbytes);
+    hipLaunchKernelGGL(k_wsplit_bf16, dim3(nch, Opad / 16), dim3(128), 0, st, k, wfr, flg, G.C, G.O, Opad);
+    const int ls = launch_nt(nt, [&](auto n) {
+        hipLaunchKernelGGL((k_hexconv_mfma_bf16d<Tout, n()>), grid, blk, 0, st, xx, wfr, flg, b, yy, G, Opad);
+    });
+    const hipError_t fe = hipFreeAsync(ws, st);
+    return ls != HG_OK ? ls : (int)fe;
+}
+
 // Runs the kernel conv_fwd_route names; HG_EUNSUP when that is none of this file's.
 int conv_mfma_try(const void* x, const float* k, const float* b, void* y, int x_dtype,
                   int y_dtype, int64_t B, int64_t C, int64_t O, int64_t h, int64_t w, int radius,
                   int stride, int padding, int dilation, int groups, int off, int pad_mode,
                   double pad_value, const Epilogue& epi, hipStream_t st) {
-    const int route = conv_fwd_route(x_dtype, HG_F32, y_dtype, B, C, O, h, w, radius, stride, padding,
-                                     dilation, groups, off, pad_mode, pad_value,
-                                     (unsigned)(reinterpret_cast<uintptr_t>(x) & 15));
+    MfmaGeom G;
+    int nt;
+    const int route = fwd_route(x_dtype, HG_F32, y_dtype, B, C, O, h, w, radius, stride, padding,
+                                dilation, groups, off, pad_mode, pad_value,
+                                (unsigned)(reinterpret_cast<uintptr_t>(x) & 15), G, nt);
     if (route == HG_CONV_FWD_OTHER) return HG_EUNSUP;
-    MfmaGeom G = {};
-    if (!conv_mfma_forward_geom(G, B, C, O, h, w, padding, off, pad_mode, pad_value, stride))
-        return HG_EUNSUP;
     G.epi = epi;
-    const int nt = conv_mfma_nt(G.O);
-    G.nto = (G.O + 16 * nt - 1) / (16 * nt);
     if (route == HG_CONV_FWD_MFMA_F32) return conv_mfma_launch_f32(x, k, b, y, x_dtype, y_dtype, G, nt, st, stride);
-    const int64_t blocks = B * (int64_t)G.ntq * G.ntr * G.nto;
-    const dim3 grid((unsigned)blocks), blk(CM_THREADS);
-    if (route == HG_CONV_FWD_MFMA_BF16_DMA) {
-        const int nch = (G.C + CM_CC - 1) / CM_CC, Opad = G.nto * 16 * nt;
-        const size_t wbytes = (size_t)nch * 6 * Opad * 64, fbytes = (size_t)nch * (Opad / 16) * 4;
-        void* ws = nullptr;
-        hipError_t e = hipMallocAsync(&ws, wbytes + fbytes, st);
-        if (e != hipSuccess) return (int)e;
-        cm_u4* wfr = static_cast<cm_u4*>(ws);
-        int* flg = reinterpret_cast<int*>(static_cast<char*>(ws) + wbytes);
-        hipLaunchKernelGGL(k_wsplit_bf16, dim3(nch, Opad / 16), dim3(128), 0, st, k, wfr, flg, G.C, G.O, Opad);
-#define HG_CD_LAUNCH2(TO, NT_)                                                                \
-        hipLaunchKernelGGL((k_hexconv_mfma_bf16d<TO, NT_>), grid, blk, 0, st, (const __bf16*)x, wfr, flg, b, (TO*)y, G, Opad);
-#define HG_CD_LAUNCH(TO)                                                                      \
-        if (nt == 2) { HG_CD_LAUNCH2(TO, 2) } else { HG_CD_LAUNCH2(TO, 4) }
-        if (y_dtype == HG_BF16) { HG_CD_LAUNCH(__bf16) } else { HG_CD_LAUNCH(float) }
-#undef HG_CD_LAUNCH
-#undef HG_CD_LAUNCH2
-        const int ls = launch_status();
-        const hipError_t fe = hipFreeAsync(ws, st);
-        return ls != HG_OK ? ls : (int)fe;
-    }
-#define HG_CB_LAUNCH(KN, TO)                                                                  \
-    if (nt == 2)                                                                              \
-        hipLaunchKernelGGL((KN<TO, 2>), grid, blk, 0, st, (const __bf16*)x, k, b, (TO*)y, G); \
-    else                                                                                      \
-        hipLaunchKernelGGL((KN<TO, 4>), grid, blk, 0, st, (const __bf16*)x, k, b, (TO*)y, G); \
-    return launch_status();
-    if (stride == 2) {
-        if (y_dtype == HG_BF16) { HG_CB_LAUNCH(k_hexconv_mfma_bf16_s2, __bf16) }
-        HG_CB_LAUNCH(k_hexconv_mfma_bf16_s2, float)
-    }
-    if (y_dtype == HG_BF16) { HG_CB_LAUNCH(k_hexconv_mfma_bf16, __bf16) }
-    HG_CB_LAUNCH(k_hexconv_mfma_bf16, float)
-#undef HG_CB_LAUNCH
+    return y_dtype == HG_BF16 ? launch_bf16<__bf16>(route, x, k, b, y, G, nt, stride, st)
+                              : launch_bf16<float>(route, x, k, b, y, G, nt, stride, st);
+}
+
+template <typename TI, typename TO>
+static int launch_f32(const void* x, const float* k, const float* b, void* y, const MfmaGeom& G,
+                      int nt, int stride, hipStream_t st) {
+    const dim3 grid((unsigned)(G.B * G.ntq * G.ntr * G.nto)), blk(CM_THREADS);
+    return launch_nt(nt, [&](auto n) {
+        auto kn = stride == 2 ? k_hexconv_mfma_s2<TI, TO, n()> : k_hexconv_mfma<TI, TO, n()>;
+        hipLaunchKernelGGL(kn, grid, blk, 0, st, static_cast<const TI*>(x), k, b, static_cast<TO*>(y), G);
+    });
 }
 
 int conv_mfma_launch_f32(const void* x, const float* k, const float* b, void* y, int x_dtype,
                          int y_dtype, const MfmaGeom& G, int nt, hipStream_t st, int stride) {
     const int64_t blocks = G.B * (int64_t)G.ntq * G.ntr * G.nto;
     if (blocks > INT_MAX || blocks <= 0) return blocks == 0 ? HG_OK : HG_EUNSUP;
-    const dim3 grid((unsigned)blocks), blk(CM_THREADS);
-#define HG_CM_LAUNCH(TI, TO)                                                                  \
-    if (stride == 2 && nt == 2)                                                               \
-        hipLaunchKernelGGL((k_hexconv_mfma_s2<TI, TO, 2>), grid, blk, 0, st, (const TI*)x, k, b, (TO*)y, G); \
-    else if (stride == 2)                                                                     \
-        hipLaunchKernelGGL((k_hexconv_mfma_s2<TI, TO, 4>), grid, blk, 0, st, (const TI*)x, k, b, (TO*)y, G); \
-    else if (nt == 2)                                                                         \
-        hipLaunchKernelGGL((k_hexconv_mfma<TI, TO, 2>), grid, blk, 0, st, (const TI*)x, k, b, (TO*)y, G); \
-    else                                                                                      \
-        hipLaunchKernelGGL((k_hexconv_mfma<TI, TO, 4>), grid, blk, 0, st, (const TI*)x, k, b, (TO*)y, G); \
-    return launch_status();
     switch (x_dtype) {
     case HG_BF16:
-        if (y_dtype == HG_BF16) { HG_CM_LAUNCH(__bf16, __bf16) }
-        if (y_dtype == HG_F32) { HG_CM_LAUNCH(__bf16, float) }
+        if (y_dtype == HG_BF16) return launch_f32<__bf16, __bf16>(x, k, b, y, G, nt, stride, st);
+        if (y_dtype == HG_F32) return launch_f32<__bf16, float>(x, k, b, y, G, nt, stride, st);
         return HG_EUNSUP;
     case HG_F16:
-        if (y_dtype == HG_F16) { HG_CM_LAUNCH(_Float16, _Float16) }
-        if (y_dtype == HG_F32) { HG_CM_LAUNCH(_Float16, float) }
+        if (y_dtype == HG_F16) return launch_f32<_Float16, _Float16>(x, k, b, y, G, nt, stride, st);
+        if (y_dtype == HG_F32) return launch_f32<_Float16, float>(x, k, b, y, G, nt, stride, st);
         return HG_EUNSUP;
     case HG_F32:
-        if (y_dtype == HG_F32) { HG_CM_LAUNCH(float, float) }
-        if (y_dtype == HG_BF16) { HG_CM_LAUNCH(float, __bf16) }
-        if (y_dtype == HG_F16) { HG_CM_LAUNCH(float, _Float16) }
+        if (y_dtype == HG_F32) return launch_f32<float, float>(x, k, b, y, G, nt, stride, st);
+        if (y_dtype == HG_BF16) return launch_f32<float, __bf16>(x, k, b, y, G, nt, stride, st);
+        if (y_dtype == HG_F16) return launch_f32<float, _Float16>(x, k, b, y, G, nt, stride, st);
         return HG_EUNSUP;
     default:
         return HG_EUNSUP;
     }
-#undef HG_CM_LAUNCH
 }
 
 }  // namespace hg

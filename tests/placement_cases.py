@@ -531,8 +531,9 @@ conv("conv_fused_md1_bf16", "tests/test_gpu_fused_conv.py::test_fused_conv_16bit
 conv("conv_fused_md1_f16_c1", "tests/test_gpu_fused_conv.py::test_fused_conv_16bit_vs_stream_kernel",
      2, 1, 1, R1 + 7, OWN1 + 2, F16, F32, close(1e-5))
 # conv_mfma.hip: f32, bf16 register-staged, bf16 LDS-DMA.  A source that is not 4-B aligned
-# keeps the register staging (conv_mfma.hip:722), bit-identical to the DMA kernel:
-# tests/test_gpu_conv_mfma.py:277-289 and :309-325
+# keeps the register staging (conv_fwd_route's alignment condition), bit-identical to the DMA
+# kernel: tests/test_gpu_conv_mfma.py, test_mfma_bf16_dma_bit_identical_to_register_staging and
+# test_mfma_bf16_dma_vs_oracle_and_unaligned
 conv("conv_mfma_f32", MF + "test_mfma_conv_fp32_vs_oracle", 2, 16, 16, 33, 70, F32, F32, close(1e-5))
 conv("conv_mfma_bf16_regs", MF + "test_mfma_bf16_conv_vs_oracle", 2, 13, 20, 30, 260, BF16, F32,
      close(1e-5), env={"HYGRID_CONV_DMA": "0"})

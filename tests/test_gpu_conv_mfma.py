@@ -227,31 +227,6 @@ def test_mfma_bf16_nan_positions_match_generic():
     torch.testing.assert_close(y[fin], ref[fin], rtol=1e-5, atol=1e-5 * float(ref[fin].abs().max()))
 
 
-def test_mfma_bf16_exact_weights_keep_inf():
-    """Weights exactly representable in bf16 (Gaussian-style taps 1/4, 1/8, ..., and zeros):
-    every chunk's second and third weight parts are 0, so the kernel runs only the first
-    part's MFMAs (conv_mfma.hip: nparts) and an infinite input times a weight stays +-Inf,
-    exactly as the generic kernel's fp32 products: the same NaN and Inf positions and signs,
-    finite outputs within 1e-5."""
-    B, C, O_, h, w = 1, 16, 16, 20, 70
-    g = torch.Generator().manual_seed(21)
-    k = (torch.randint(-4, 5, (O_, C, 1, 7), generator=g).float() / 8.0).to(DEV)
-    b = (torch.randint(-4, 5, (O_,), generator=g).float() / 4.0).to(DEV)
-    x = _bf16_input((B, C, h, w), 9)
-    x[0, 3, 0, 5] = float("nan")
-    x[0, 7, 19, 69] = float("inf")
-    x[0, 9, 10, 30] = float("-inf")
-    y = ops.hexconv2d(x, k, b, 1, 2, padding=1, out_dtype=torch.float32)
-    ref = _generic(ops.hexconv2d, x, k, b, 1, 2, padding=1, out_dtype=torch.float32)
-    assert torch.equal(torch.isnan(y), torch.isnan(ref))
-    assert torch.equal(torch.isinf(y), torch.isinf(ref))
-    assert torch.equal(y[torch.isinf(ref)], ref[torch.isinf(ref)])
-    fin = torch.isfinite(ref)
-    torch.testing.assert_close(y[fin], ref[fin], rtol=1e-5, atol=1e-5 * float(ref[fin].abs().max()))
-
-
-# ---- bf16 inputs staged by LDS-DMA (k_hexconv_mfma_bf16d, round 4) ------------------------
-
 def _with_env(name, value, fn, *args, **kw):
     old = os.environ.get(name)
     os.environ[name] = value
@@ -264,6 +239,73 @@ def _with_env(name, value, fn, *args, **kw):
             del os.environ[name]
         else:
             os.environ[name] = old
+
+
+def _plan(x, k, out_dtype, pad, off=0):
+    B, C, h, w = x.shape
+    return ops.hexconv2d_forward_plan(x.dtype, k.dtype, out_dtype, B, C, k.shape[0], h, w, 2,
+                                      padding=pad, even_odd_offset=off)
+
+
+def _on_route(dma, fn, *args, **kw):
+    """fn on the default route (the LDS-DMA kernel, split by k_wsplit_bf16) or, dma = False, with
+    HYGRID_CONV_DMA=0 (the register-staged kernel, which splits its weights itself)."""
+    return fn(*args, **kw) if dma else _with_env("HYGRID_CONV_DMA", "0", fn, *args, **kw)
+
+
+def _exact_weights_keep_inf(dma):
+    """Weights exactly representable in bf16 (Gaussian-style taps 1/4, 1/8, ..., and zeros):
+    every chunk's second and third weight parts are 0, so the kernel runs only the first
+    part's MFMAs (conv_mfma.hip: nparts) and an infinite input times a weight stays +-Inf,
+    exactly as the generic kernel's fp32 products: the same NaN and Inf positions and signs,
+    finite outputs within 1e-5.  On both bf16 kernels: the plan names the one that runs."""
+    from HyGrid import _abi
+    B, C, O_, h, w = 1, 16, 16, 20, 70
+    g = torch.Generator().manual_seed(21)
+    k = (torch.randint(-4, 5, (O_, C, 1, 7), generator=g).float() / 8.0).to(DEV)
+    b = (torch.randint(-4, 5, (O_,), generator=g).float() / 4.0).to(DEV)
+    x = _bf16_input((B, C, h, w), 9)
+    x[0, 3, 0, 5] = float("nan")
+    x[0, 7, 19, 69] = float("inf")
+    x[0, 9, 10, 30] = float("-inf")
+    assert _on_route(dma, _plan, x, k, torch.float32, 1, 1) == (
+        _abi.HG_CONV_FWD_MFMA_BF16_DMA if dma else _abi.HG_CONV_FWD_MFMA_BF16)
+    y = _on_route(dma, ops.hexconv2d, x, k, b, 1, 2, padding=1, out_dtype=torch.float32)
+    ref = _generic(ops.hexconv2d, x, k, b, 1, 2, padding=1, out_dtype=torch.float32)
+    assert torch.equal(torch.isnan(y), torch.isnan(ref))
+    assert torch.equal(torch.isinf(y), torch.isinf(ref))
+    assert torch.equal(y[torch.isinf(ref)], ref[torch.isinf(ref)])
+    fin = torch.isfinite(ref)
+    torch.testing.assert_close(y[fin], ref[fin], rtol=1e-5, atol=1e-5 * float(ref[fin].abs().max()))
+
+
+def test_mfma_bf16_exact_weights_keep_inf():
+    _exact_weights_keep_inf(True)
+
+
+def test_mfma_bf16_exact_weights_keep_inf_register_staged():
+    _exact_weights_keep_inf(False)
+
+
+@pytest.mark.parametrize("dma", [True, False])
+def test_mfma_bf16_mixed_exact_and_split_chunks(dma):
+    """C = 16: the chunk of channels 0-7 has bf16-exact weights (one part's MFMAs), the chunk of
+    channels 8-15 random ones (all three parts), in one accumulation; finite inputs, 1e-5 against
+    the generic kernel.  12 x 140: interior (DMA-staged) and border tiles."""
+    from HyGrid import _abi
+    B, C, O_, h, w = 1, 16, 16, 12, 140
+    k, b = _weights(O_, C, 33)
+    g = torch.Generator().manual_seed(34)
+    k[:, :8] = (torch.randint(-4, 5, (O_, 8, 1, 7), generator=g).float() / 8.0).to(DEV)
+    x = _bf16_input((B, C, h, w), 35)
+    assert _on_route(dma, _plan, x, k, torch.float32, 1) == (
+        _abi.HG_CONV_FWD_MFMA_BF16_DMA if dma else _abi.HG_CONV_FWD_MFMA_BF16)
+    y = _on_route(dma, ops.hexconv2d, x, k, b, 0, 2, padding=1, out_dtype=torch.float32)
+    ref = _generic(ops.hexconv2d, x, k, b, 0, 2, padding=1, out_dtype=torch.float32)
+    torch.testing.assert_close(y, ref, rtol=1e-5, atol=1e-5 * float(ref.abs().max()))
+
+
+# ---- bf16 inputs staged by LDS-DMA (k_hexconv_mfma_bf16d, round 4) ------------------------
 
 
 DMA_CASES = [  # (B, C, O, h, w): interior tiles (DMA-staged P) and border tiles in each

@@ -298,6 +298,41 @@ def test_s2_nonfinite_positions_match_generic_bf16():
     torch.testing.assert_close(y[fin], ref[fin], rtol=1e-5, atol=1e-5 * float(ref[fin].abs().max()))
 
 
+def test_s2_bf16_exact_weights_keep_inf():
+    """test_mfma_bf16_exact_weights_keep_inf at stride 2: bf16-exact weights run one part's MFMAs
+    on the kernel's own weight split, so an infinite input times a weight stays +-Inf as in the
+    generic kernel: the same NaN and Inf positions and signs, finite outputs within 1e-5."""
+    B, C, O_, h, w = NF_CASE
+    g = torch.Generator().manual_seed(21)
+    k = (torch.randint(-4, 5, (O_, C, 1, 7), generator=g).float() / 8.0).to(DEV)
+    b = (torch.randint(-4, 5, (O_,), generator=g).float() / 4.0).to(DEV)
+    x = _plant(_bf16_input((B, C, h, w), 9))
+    assert _plan(x, k, F32, NF_PAD, NF_OFF) == MBF
+    y = ops.hexconv2d(x, k, b, NF_OFF, 2, stride=2, padding=NF_PAD, out_dtype=F32)
+    ref = _generic(ops.hexconv2d, x, k, b, NF_OFF, 2, stride=2, padding=NF_PAD, out_dtype=F32)
+    assert bool(torch.isinf(ref).any())                   # a planted Inf is read
+    assert torch.equal(torch.isnan(y), torch.isnan(ref))
+    assert torch.equal(torch.isinf(y), torch.isinf(ref))
+    assert torch.equal(y[torch.isinf(ref)], ref[torch.isinf(ref)])
+    fin = torch.isfinite(ref)
+    torch.testing.assert_close(y[fin], ref[fin], rtol=1e-5, atol=1e-5 * float(ref[fin].abs().max()))
+
+
+def test_s2_bf16_mixed_exact_and_split_chunks():
+    """C = 16: the chunk of channels 0-7 has bf16-exact weights (one part's MFMAs), the chunk of
+    channels 8-15 random ones (all three parts), in one accumulation; finite inputs, 1e-5 against
+    the generic kernel."""
+    B, C, O_, h, w = 1, 16, 16, 14, 40
+    k, b = _weights(O_, C, 33)
+    g = torch.Generator().manual_seed(34)
+    k[:, :8] = (torch.randint(-4, 5, (O_, 8, 1, 7), generator=g).float() / 8.0).to(DEV)
+    x = _bf16_input((B, C, h, w), 35)
+    assert _plan(x, k, F32, 1) == MBF
+    y = ops.hexconv2d(x, k, b, 0, 2, stride=2, padding=1, out_dtype=F32)
+    ref = _generic(ops.hexconv2d, x, k, b, 0, 2, stride=2, padding=1, out_dtype=F32)
+    torch.testing.assert_close(y, ref, rtol=1e-5, atol=1e-5 * float(ref.abs().max()))
+
+
 # ---- training: MFMA forward, generic backward ---------------------------------------------------
 
 def test_s2_autograd_forward_mfma_backward_generic():

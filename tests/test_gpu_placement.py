@@ -15,9 +15,11 @@ inside sentinel-filled arenas, at base offsets that leave the base 2-B (16-bit d
 
 Exceptions to (c), each from the host code's own documentation:
   * tri_up, hexresize_down and the conv_mfma DMA kernel test the source's alignment and fall
-    back (tri_up.hip:427, hexresize_down.hip:358-359, conv_mfma.hip:722).  Their existing tests
-    assert the two kernels of each pair bit-identical (tests/test_gpu_triup.py:160-168,
-    tests/test_gpu_hexdown.py:128-138, tests/test_gpu_conv_mfma.py:277-289 and :309-325), so (c)
+    back (tri_up.hip:427, hexresize_down.hip:358-359, conv_mfma.hip: conv_fwd_route's alignment
+    condition).  Their existing tests assert the two kernels of each pair bit-identical
+    (tests/test_gpu_triup.py:160-168, tests/test_gpu_hexdown.py:128-138,
+    tests/test_gpu_conv_mfma.py: test_mfma_bf16_dma_bit_identical_to_register_staging and
+    test_mfma_bf16_dma_vs_oracle_and_unaligned), so (c)
     holds for them as it stands; the queries have no pointer argument, so which kernel ran at a
     given base is not observable from here.
   * The pyramid level kernels and the chain decline a 16-bit source that is not 4-B aligned
