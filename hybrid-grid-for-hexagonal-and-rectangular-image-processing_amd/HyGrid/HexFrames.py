@@ -29,7 +29,7 @@ from torch.nn import init
 
 from . import ops
 
-__all__ = ["HexConv2d", "pad", "heximage_to_type1", "heximage_to_type2", "type1_to_heximage",
+__all__ = ["HexConv2d", "HexConvTranspose2d", "pad", "heximage_to_type1", "heximage_to_type2", "type1_to_heximage",
            "HexPool2d", "HexAdaptivePool2d", "HexGlobalPool2d", "max_pooling", "min_pooling",
            "average_pooling"]
 
@@ -140,6 +140,123 @@ class HexConv2d(nn.Module):
             s += ', bias=False'
         if self.padding_mode != 'zeros':
             s += ', padding_mode={padding_mode}'
+        return s.format(**self.__dict__)
+
+
+class _HexConvTranspose2dFn(torch.autograd.Function):
+    """y = A^T x + bias for the adjoint conv A (HexConvTranspose2d): d input is A itself on gy
+    (the forward kernels, on the matrix cores at stride 2), d kernel is A's d kernel with the
+    roles of input and gradient swapped, d bias the channel sum."""
+
+    @staticmethod
+    def forward(ctx, x, kernel, bias, cfg, output_size):
+        y = ops.hexconv_transpose2d(x, kernel, bias, cfg["off"], cfg["r"], cfg["stride"],
+                                    cfg["pad"], cfg["dilation"], cfg["groups"], output_size,
+                                    cfg["out_dtype"])
+        ctx.save_for_backward(x, kernel)
+        ctx.cfg = cfg
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, kernel = ctx.saved_tensors
+        cfg = ctx.cfg
+        need_x, need_k, need_b = ctx.needs_input_grad[:3]
+        gy = gy.contiguous()
+        gx = gk = gb = None
+        if need_x:
+            gx = ops.hexconv2d(gy, kernel, None, cfg["off"], cfg["r"], cfg["stride"], cfg["pad"],
+                               cfg["dilation"], cfg["groups"], "constant", 0.0,
+                               x.dtype if x.dtype.is_floating_point else None)
+        if need_k:
+            _, gk, _ = ops.hexconv2d_backward(x, gy, kernel, None, cfg, False, True, False)
+        if need_b:
+            gb = gy.sum((0, 2, 3)).to(kernel.dtype)
+        return gx, gk, gb, None, None
+
+
+class HexConvTranspose2d(nn.Module):
+    """Transposed hexagonal convolution: the exact adjoint of
+    HexConv2d(out_channels, in_channels, even_odd_offset, hexkernel_radius, stride, padding,
+    dilation, groups, padding_mode='constant', padding_value=0), plus a bias; at stride 2 the
+    learnable x2 upsampler that undoes a stride-2 HexConv2d's change of size.
+
+    even_odd_offset is the row offset of the image the layer PRODUCES (the adjoint conv's
+    input); its own input has offset 0, as HexConv2d.out_even_odd_offset.  `kernel` is
+    [in_channels, out_channels // groups, 1, K] (torch's transposed-conv convention, and the
+    adjoint conv's own `kernel`), `bias` [out_channels]; initialised by HexConv2d's sequence.
+
+    forward(input, output_size=None): stride s leaves s valid sizes per axis, every (h, w)
+    with hexconv2d_out_shape(h, w, ...) == input's (hin, win).  The default is the largest
+    valid h and the smallest valid w: (2 hin + 2 - 2p, 2 win + 2 - 2p) at radius 2, stride 2,
+    exactly x2 at padding 1; any other output_size raises ValueError.  Output samples no tap
+    reaches (at padding 0 the last row and columns of the larger sizes) hold the bias.
+
+    Radius 2, stride 2, dilation 1, groups 1, padding 0..2 and out_channels >= 16 run on the
+    matrix cores (ops.hexconv_transpose2d_plan tells).  Backward: d input is the adjoint
+    HexConv2d's forward (matrix cores at stride 2); d kernel is ops.hexconv2d_backward with
+    input and gradient swapped, which at stride 2 still runs the generic kernel."""
+
+    def __init__(self, in_channels, out_channels, even_odd_offset, hexkernel_radius, stride=1,
+                 padding=0, dilation=1, groups=1, bias=True):
+        super().__init__()
+        if in_channels % groups != 0:
+            raise ValueError('in_channels must be divisible by groups')
+        if out_channels % groups != 0:
+            raise ValueError('out_channels must be divisible by groups')
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.even_odd_offset = even_odd_offset
+        self.in_even_odd_offset = 0
+        self.hexkernel_radius = hexkernel_radius
+        self.kernelnum = 3 * hexkernel_radius ** 2 - 3 * hexkernel_radius + 1
+        self.stride = stride
+        self.pad = padding
+        self.dilation = dilation
+        self.groups = groups
+        self.b = bias
+        self.out_dtype = None       # None = torch.get_default_dtype(), as HexConv2d
+        self.kernel = nn.Parameter(torch.empty([in_channels, out_channels // groups, 1,
+                                                self.kernelnum], dtype=torch.float))
+        if bias:
+            self.bias = nn.Parameter(torch.empty([out_channels, ]))
+        else:
+            self.register_parameter('bias', None)
+        self.reset_parameters()
+
+    reset_parameters = HexConv2d.reset_parameters
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        wk, kk = prefix + 'weight', prefix + 'kernel'
+        if wk in state_dict and kk not in state_dict:
+            state_dict[kk] = state_dict.pop(wk)
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def _cfg(self):
+        return dict(off=int(self.even_odd_offset), r=self.hexkernel_radius, stride=self.stride,
+                    pad=self.pad, dilation=self.dilation, groups=self.groups,
+                    padding_mode='constant', padding_value=0.0, out_dtype=self.out_dtype)
+
+    def output_shape(self, hin, win, output_size=None):
+        return ops.hexconv_transpose2d_out_shape(hin, win, self.hexkernel_radius, self.stride,
+                                                 self.pad, self.dilation, output_size)
+
+    def forward(self, input: Tensor, output_size=None) -> Tensor:
+        while input.dim() < 4:
+            input = input.unsqueeze(0)
+        if output_size is not None:
+            output_size = tuple(int(v) for v in tuple(output_size)[-2:])
+        return _HexConvTranspose2dFn.apply(input, self.kernel, self.bias, self._cfg(), output_size)
+
+    def extra_repr(self):
+        s = ('{in_channels}, {out_channels}, kernel_radius={hexkernel_radius}'
+             ', stride={stride}, padding={pad}')
+        if self.dilation != 1:
+            s += ', dilation={dilation}'
+        if self.groups != 1:
+            s += ', groups={groups}'
+        if self.bias is None:
+            s += ', bias=False'
         return s.format(**self.__dict__)
 
 

@@ -54,9 +54,11 @@ class _Registry(dict):
 if HAVE_MMCV:
     CONV_LAYERS = _MM_CONV
     CONV_LAYERS.register_module('HexConv2d', module=hnn.HexConv2d, force=True)
+    CONV_LAYERS.register_module('HexConvTranspose2d', module=hnn.HexConvTranspose2d, force=True)
 else:
     CONV_LAYERS = _Registry()
     CONV_LAYERS.register_module('HexConv2d', module=hnn.HexConv2d)
+    CONV_LAYERS.register_module('HexConvTranspose2d', module=hnn.HexConvTranspose2d)
 
 _PADDING = {'zero': nn.ZeroPad2d, 'reflect': nn.ReflectionPad2d,
             'replicate': nn.ReplicationPad2d}

@@ -443,6 +443,123 @@ def hexconv2d_forward_plan(x_dtype, w_dtype, y_dtype, batch, in_channels, out_ch
     return kern.value
 
 
+def _convt_valid_sizes(hin, win, radius, stride, padding, dilation):
+    """([h...], [w...]) ascending: every output size a HexConv2d of these arguments maps onto
+    (hin, win), found by searching hexconv2d_out_shape around its inverse."""
+    kh = (2 * radius - 2) * dilation + 1
+    kw = 2 * dilation * (2 * radius - 2) + 1
+    h0 = (hin - 1) * stride + kh - 2 * padding
+    w0 = (2 * stride * (win - 1) + stride + kw + 1) // 2 - 2 * padding
+    hs, ws = [], []
+    for h in range(max(h0 - 1, 1), h0 + stride + 1):
+        for w in range(max(w0 - 1, 1), w0 + stride + 1):
+            try:
+                ho, wo = hexconv2d_out_shape(h, w, radius, stride, padding, dilation)
+            except ValueError:
+                continue
+            if ho == hin and h not in hs:
+                hs.append(h)
+            if wo == win and w not in ws:
+                ws.append(w)
+    return hs, ws
+
+
+def hexconv_transpose2d_out_shape(hin, win, radius, stride=1, padding=0, dilation=1,
+                                  output_size=None):
+    """Output size (h, w) of hexconv_transpose2d for a (hin, win) input.  Valid sizes are those
+    the adjoint HexConv2d maps back: hexconv2d_out_shape(h, w, radius, stride, padding, dilation)
+    == (hin, win); stride s leaves s choices per axis.  output_size=None picks the largest valid
+    h and the smallest valid w, (2 hin + 2 - 2p, 2 win + 2 - 2p) at radius 2, stride 2: exactly
+    x2 at padding 1.  Any other output_size raises ValueError."""
+    hin, win = int(hin), int(win)
+    if hin < 1 or win < 1:
+        raise ValueError(f"hexconv_transpose2d: empty input {(hin, win)}")
+    hs, ws = _convt_valid_sizes(hin, win, radius, stride, padding, dilation)
+    if not hs or not ws:
+        raise ValueError(f"hexconv_transpose2d: no output size maps onto {(hin, win)}")
+    if output_size is None:
+        return max(hs), min(ws)
+    h, w = (int(v) for v in tuple(output_size)[-2:])
+    if h not in hs or w not in ws:
+        raise ValueError(f"hexconv_transpose2d: output_size {(h, w)} is not one of "
+                         f"{[(a, b) for a in hs for b in ws]} for input {(hin, win)}")
+    return h, w
+
+
+def hexconv_transpose2d_plan(x_dtype, w_dtype, y_dtype, batch, in_channels, out_channels, hin,
+                             win, h, w, radius, stride=1, padding=0, dilation=1, groups=1,
+                             even_odd_offset=0):
+    """Which route hexconv_transpose2d takes for this layer (hg_hexconv_transpose2d_plan):
+    _abi.HG_CONVT_MFMA_S2 (k_hexconvt_s2 on the matrix cores) or _abi.HG_CONVT_ADJOINT (the
+    adjoint conv's d input, then a bias add), HYGRID_CONVT_MFMA included.  Nothing is launched
+    and no device is needed.  dtypes: torch dtypes or hg_dtype codes."""
+    xd, wd, yd = (d if isinstance(d, int) else _abi.dtype_code(d)
+                  for d in (x_dtype, w_dtype, y_dtype))
+    kern = ctypes.c_int()
+    st = _abi.lib().hg_hexconv_transpose2d_plan(
+        xd, wd, yd, int(batch), int(in_channels), int(out_channels), int(hin), int(win), int(h),
+        int(w), int(radius), int(stride), int(padding), int(dilation), int(groups),
+        int(even_odd_offset), ctypes.byref(kern))
+    _abi.check(st, "hg_hexconv_transpose2d_plan")
+    return kern.value
+
+
+def hexconv_transpose2d_taps(even_odd_offset, padding, row_class, col_class):
+    """[(t, rofs, qofs), ...] of output class (iy mod 4, ix mod 2) at radius 2, stride 2: the
+    table k_hexconvt_s2 is launched with (hg_hexconv_transpose2d_taps; host only)."""
+    out = (ctypes.c_int * 7)()
+    st = _abi.lib().hg_hexconv_transpose2d_taps(int(even_odd_offset), int(padding),
+                                                int(row_class), int(col_class), out)
+    _abi.check(st, "hg_hexconv_transpose2d_taps")
+    return [tuple(out[1 + 3 * j:4 + 3 * j]) for j in range(out[0])]
+
+
+def hexconv_transpose2d(x, kernel, bias, even_odd_offset, radius, stride=1, padding=0,
+                        dilation=1, groups=1, output_size=None, out_dtype=None):
+    """HexConvTranspose2d forward (hg_hexconv_transpose2d): the adjoint of
+    hexconv2d(., kernel, None, even_odd_offset, radius, stride, padding, dilation, groups) with
+    constant zero padding, plus bias.  x: (B, I, hin, win) -> (B, O, h, w), (h, w) by
+    hexconv_transpose2d_out_shape.  kernel: (I, O/groups, 1, K) or (I, O/groups, K), float32 /
+    float64 (the accumulation dtype); even_odd_offset is the output's row offset.
+    On the adjoint route (hexconv_transpose2d_plan) x is converted to the kernel's dtype and the
+    result to out_dtype, as hexconv2d_backward does; the matrix-core route reads x and writes
+    out_dtype directly."""
+    _abi.require_device(x)
+    while x.dim() < 4:
+        x = x.unsqueeze(0)
+    x = x.contiguous()
+    B, I, hin, win = (int(s) for s in x.shape)
+    k = kernel.detach()
+    if k.dtype not in (torch.float32, torch.float64):
+        k = k.float()
+    k = k.reshape(k.shape[0], k.shape[1], -1).contiguous()
+    if int(k.shape[0]) != I:
+        raise ValueError(f"kernel expects {int(k.shape[0])} input channels, got {I}")
+    O = int(k.shape[1]) * groups
+    b = None
+    if bias is not None:
+        b = bias.detach().to(k.dtype).contiguous()
+        if b.numel() != O:
+            raise ValueError(f"bias must have {O} elements")
+    if out_dtype is None:
+        out_dtype = torch.get_default_dtype()
+    h, w = hexconv_transpose2d_out_shape(hin, win, radius, stride, padding, dilation, output_size)
+    if not x.dtype.is_floating_point:
+        x = x.to(k.dtype)
+    route = hexconv_transpose2d_plan(x.dtype, k.dtype, out_dtype, B, I, O, hin, win, h, w, radius,
+                                     stride, padding, dilation, groups, even_odd_offset)
+    y_dtype = out_dtype
+    if route == _abi.HG_CONVT_ADJOINT:
+        x, y_dtype = x.to(k.dtype), k.dtype
+    y = torch.empty((B, O, h, w), dtype=y_dtype, device=x.device)
+    st = _abi.lib().hg_hexconv_transpose2d(
+        _abi.ptr(x), _abi.ptr(k), _abi.ptr(b), _abi.ptr(y), _abi.dtype_code(x.dtype),
+        _abi.dtype_code(k.dtype), _abi.dtype_code(y_dtype), B, I, O, hin, win, h, w, radius,
+        stride, padding, dilation, groups, int(even_odd_offset), _abi.stream_of(x))
+    _abi.check(st, "hg_hexconv_transpose2d")
+    return y if y_dtype == out_dtype else y.to(out_dtype)
+
+
 def hex_to_type1(x, even_odd_offset, row_repeat=1, out_dtype=None):
     """Offset-row hex raster (..., H, W) -> type1 (..., H*row_repeat, 2W+1) on the GPU
     (hg_hex_to_type1): row_repeat 1 = HexFrames.heximage_to_type1 (HexFrames.py:417-445),
