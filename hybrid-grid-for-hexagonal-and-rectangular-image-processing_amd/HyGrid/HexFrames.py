@@ -54,12 +54,17 @@ class _HexConv2dFn(torch.autograd.Function):
         x, kernel, bias = ctx.saved_tensors
         cfg = ctx.cfg
         need_x, need_k, need_b = ctx.needs_input_grad[:3]
-        gx, gk, gb = ops.hexconv2d_backward(gy, x, kernel, bias, cfg, need_x, need_k, need_b)
+        gx, gk, gb = ops.hexconv2d_grads(gy, x, kernel, bias, cfg, need_x, need_k, need_b)
         return gx, gk, gb, None
 
 
 class HexConv2d(nn.Module):
-    """Hexagonal convolution; reference HexFrames.py:22-185."""
+    """Hexagonal convolution; reference HexFrames.py:22-185.
+
+    Backward (ops.hexconv2d_grads) picks a kernel per gradient; ops.hexconv2d_training_plan
+    tells which.  A wide radius-2 layer trains on the matrix cores at stride 1 and at stride 2:
+    there d kernel / d bias run k_hexconv_bwd_weight_mfma_s2 and d input, with constant padding
+    and 16 input channels or more, is the transposed layer's forward (k_hexconvt_s2)."""
 
     def __init__(self, in_channels, out_channels, even_odd_offset, hexkernel_radius, stride=1,
                  padding=0, dilation=1, groups=1, bias=True,
@@ -169,7 +174,7 @@ class _HexConvTranspose2dFn(torch.autograd.Function):
                                cfg["dilation"], cfg["groups"], "constant", 0.0,
                                x.dtype if x.dtype.is_floating_point else None)
         if need_k:
-            _, gk, _ = ops.hexconv2d_backward(x, gy, kernel, None, cfg, False, True, False)
+            _, gk, _ = ops.hexconv2d_grads(x, gy, kernel, None, cfg, False, True, False)
         if need_b:
             gb = gy.sum((0, 2, 3)).to(kernel.dtype)
         return gx, gk, gb, None, None
@@ -194,8 +199,9 @@ class HexConvTranspose2d(nn.Module):
 
     Radius 2, stride 2, dilation 1, groups 1, padding 0..2 and out_channels >= 16 run on the
     matrix cores (ops.hexconv_transpose2d_plan tells).  Backward: d input is the adjoint
-    HexConv2d's forward (matrix cores at stride 2); d kernel is ops.hexconv2d_backward with
-    input and gradient swapped, which at stride 2 still runs the generic kernel."""
+    HexConv2d's forward (matrix cores at stride 2); d kernel is ops.hexconv2d_grads with input
+    and gradient swapped, at stride 2 on the matrix cores as well (k_hexconv_bwd_weight_mfma_s2;
+    ops.hexconv2d_training_plan tells)."""
 
     def __init__(self, in_channels, out_channels, even_odd_offset, hexkernel_radius, stride=1,
                  padding=0, dilation=1, groups=1, bias=True):

@@ -194,7 +194,7 @@ def _act_grad(y, act, slope):
 
 class _HexConvEpilogueFn(torch.autograd.Function):
     """conv + bias -> x scale + shift -> act in one launch; backward through the
-    activation (from the saved output) and the fixed affine into hexconv2d_backward."""
+    activation (from the saved output) and the fixed affine into hexconv2d_grads."""
 
     @staticmethod
     def forward(ctx, x, kernel, bias, cfg, scale, shift, act, slope):
@@ -217,7 +217,7 @@ class _HexConvEpilogueFn(torch.autograd.Function):
         if scale is not None:
             g = g * scale.to(g.dtype).view(1, -1, 1, 1)
         need_x, need_k, need_b = ctx.needs_input_grad[:3]
-        gx, gk, gb = ops.hexconv2d_backward(g, x, kernel, bias, cfg, need_x, need_k, need_b)
+        gx, gk, gb = ops.hexconv2d_grads(g, x, kernel, bias, cfg, need_x, need_k, need_b)
         return gx, gk, gb, None, None, None, None, None
 
 

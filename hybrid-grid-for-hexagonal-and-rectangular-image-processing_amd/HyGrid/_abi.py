@@ -1,4 +1,5 @@
-"""ctypes binding of libhygrid_hip.so (C ABI: include/hygrid.h, include/hygrid_layers.h).
+"""ctypes binding of libhygrid_hip.so (C ABI: include/hygrid.h, include/hygrid_layers.h,
+include/hygrid_train.h).
 
 This is the only module that touches the native library.  Everything above it
 (geometry_np, geometry_torch, HexFrames, ...) goes through `ops`, which calls
@@ -31,6 +32,7 @@ HG_PYR_FUSED, HG_PYR_FUSED_SHORT, HG_PYR_STREAM, HG_PYR_LDS = range(4)
 HG_POOL_SMALL, HG_POOL_LARGE = 0, 1
 HG_CONV_BWD_GENERIC, HG_CONV_BWD_MFMA = 0, 1
 HG_CONVT_ADJOINT, HG_CONVT_MFMA_S2 = 0, 1
+HG_CONV_WGRAD_GENERIC, HG_CONV_WGRAD_MFMA, HG_CONV_WGRAD_MFMA_S2 = range(3)
 HG_CONV_FWD_OTHER, HG_CONV_FWD_MFMA_F32, HG_CONV_FWD_MFMA_BF16, HG_CONV_FWD_MFMA_BF16_DMA = range(4)
 HG_OK, HG_EINVAL, HG_EDTYPE, HG_ESHAPE, HG_EUNSUP, HG_EOVERFLOW = 0, -1, -2, -3, -4, -5
 PAD_MODES = {"constant": 0, "zeros": 0, "reflect": 1, "replicate": 2, "circular": 3}
@@ -108,6 +110,13 @@ LAYER_SIGNATURES = {
                                     + [ctypes.POINTER(_int)], _int),
     "hg_hexconv_transpose2d_taps": ([_int] * 4 + [ctypes.POINTER(_int)], _int),
 }
+# Every symbol include/hygrid_train.h declares (the same library).
+TRAIN_SIGNATURES = {
+    "hg_hexconv2d_weight_grad": ([_vp] * 4 + [_int, _int] + [_i64] * 5 + [_int] * 7 + [_dbl, _vp],
+                                 _int),
+    "hg_hexconv2d_weight_grad_plan": ([_int, _int] + [_i64] * 5 + [_int] * 6
+                                      + [ctypes.POINTER(_int)], _int),
+}
 ABI_VERSION = 1
 
 _lib = None
@@ -126,7 +135,8 @@ def lib():
                 f"HyGrid native library not found at {LIB_PATH}; build it with "
                 "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950)")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (args, res) in list(SIGNATURES.items()) + list(LAYER_SIGNATURES.items()):
+        for name, (args, res) in (list(SIGNATURES.items()) + list(LAYER_SIGNATURES.items())
+                                  + list(TRAIN_SIGNATURES.items())):
             fn = getattr(L, name)
             fn.argtypes = args
             fn.restype = res

@@ -420,6 +420,115 @@ def hexconv2d_backward_plan(x_dtype, w_dtype, batch, in_channels, out_channels, 
     return dxk.value, dwk.value
 
 
+def _pad_mode(padding_mode):
+    pm = _abi.PAD_MODES.get(padding_mode)
+    if pm is None:
+        raise ValueError(f"unsupported padding_mode {padding_mode!r}")
+    return pm
+
+
+def hexconv2d_weight_grad_plan(x_dtype, w_dtype, batch, in_channels, out_channels, h, w, radius,
+                               stride=1, padding=0, dilation=1, groups=1, padding_mode="constant"):
+    """Which kernel hexconv2d_weight_grad runs for d kernel (+ d bias) of this layer
+    (hg_hexconv2d_weight_grad_plan): _abi.HG_CONV_WGRAD_GENERIC, _MFMA (stride 1) or _MFMA_S2
+    (stride 2), the switches HYGRID_CONV_BWD_MFMA / HYGRID_CONV_BWD_MFMA_S2 included.  Nothing is
+    launched and no device is needed.  dtypes: torch dtypes or hg_dtype codes."""
+    pm = _pad_mode(padding_mode)
+    xd = x_dtype if isinstance(x_dtype, int) else _abi.dtype_code(x_dtype)
+    wd = w_dtype if isinstance(w_dtype, int) else _abi.dtype_code(w_dtype)
+    kern = ctypes.c_int()
+    st = _abi.lib().hg_hexconv2d_weight_grad_plan(
+        xd, wd, int(batch), int(in_channels), int(out_channels), int(h), int(w), int(radius),
+        int(stride), int(padding), int(dilation), int(groups), pm, ctypes.byref(kern))
+    _abi.check(st, "hg_hexconv2d_weight_grad_plan")
+    return kern.value
+
+
+def hexconv2d_training_plan(x_dtype, w_dtype, batch, in_channels, out_channels, h, w, radius,
+                            stride=1, padding=0, dilation=1, groups=1, even_odd_offset=0,
+                            padding_mode="constant"):
+    """(d input route, d kernel route) of hexconv2d_grads for this layer.  d input: "convt_s2"
+    (stride 2, constant padding: hexconv_transpose2d on gy where hexconv_transpose2d_plan, asked
+    with the channel counts swapped, answers _abi.HG_CONVT_MFMA_S2), else what
+    hexconv2d_backward_plan says for d input, "mfma" or "generic".  d kernel: the
+    hg_conv_wgrad_kernel value of hexconv2d_weight_grad_plan.  Every switch is read as the calls
+    read it (HYGRID_CONVT_MFMA=0 also switches "convt_s2" off).  Nothing is launched and no
+    device is needed; gy is taken to have the weights' dtype, as hexconv2d_grads makes it."""
+    pm = _pad_mode(padding_mode)
+    xd = x_dtype if isinstance(x_dtype, int) else _abi.dtype_code(x_dtype)
+    wd = w_dtype if isinstance(w_dtype, int) else _abi.dtype_code(w_dtype)
+    dk_route = hexconv2d_weight_grad_plan(xd, wd, batch, in_channels, out_channels, h, w, radius,
+                                          stride, padding, dilation, groups, padding_mode)
+    floats = (_abi.HG_F16, _abi.HG_BF16, _abi.HG_F32, _abi.HG_F64)
+    if stride == 2 and pm == 0 and batch > 0 and xd in floats:
+        ho, wo = hexconv2d_out_shape(h, w, radius, stride, padding, dilation)
+        if ho > 0 and wo > 0 and hexconv_transpose2d_plan(
+                wd, wd, xd, batch, out_channels, in_channels, ho, wo, h, w, radius, stride,
+                padding, dilation, groups, even_odd_offset) == _abi.HG_CONVT_MFMA_S2:
+            return "convt_s2", dk_route
+    dxk, _ = hexconv2d_backward_plan(xd, wd, batch, in_channels, out_channels, h, w, radius,
+                                     stride, padding, dilation, groups, padding_mode)
+    return ("mfma" if dxk == _abi.HG_CONV_BWD_MFMA else "generic"), dk_route
+
+
+def hexconv2d_weight_grad(gy, x, kernel, bias, cfg, need_k=True, need_b=True):
+    """(d kernel, d bias) of hexconv2d (hg_hexconv2d_weight_grad), hexconv2d_backward's
+    arguments and contract: None for a gradient not requested (d bias also when bias is None),
+    the parameters' shapes and dtypes."""
+    _abi.require_device(gy)
+    while x.dim() < 4:
+        x = x.unsqueeze(0)
+    x = x.contiguous()
+    B, C, h, w = (int(s) for s in x.shape)
+    kdt = kernel.dtype if kernel.dtype in (torch.float32, torch.float64) else torch.float32
+    kshape = tuple(kernel.shape)
+    O, cg = int(kshape[0]), int(kshape[1])
+    K = int(kernel.numel()) // max(O * cg, 1)
+    g = gy.detach().to(kdt).contiguous()
+    dk = torch.empty((O, cg, K), dtype=kdt, device=x.device) if need_k else None
+    db = (torch.empty((O,), dtype=kdt, device=x.device)
+          if (need_b and bias is not None) else None)
+    st = _abi.lib().hg_hexconv2d_weight_grad(
+        _abi.ptr(x), _abi.ptr(g), _abi.ptr(dk), _abi.ptr(db), _abi.dtype_code(x.dtype),
+        _abi.dtype_code(kdt), B, C, O, h, w, cfg["r"], cfg["stride"], cfg["pad"], cfg["dilation"],
+        cfg["groups"], int(cfg["off"]), _pad_mode(cfg["padding_mode"]),
+        float(cfg["padding_value"]), _abi.stream_of(x))
+    _abi.check(st, "hg_hexconv2d_weight_grad")
+    gk = dk.reshape(kshape).to(kernel.dtype) if dk is not None else None
+    gb = db.to(bias.dtype) if db is not None else None
+    return gk, gb
+
+
+def hexconv2d_grads(gy, x, kernel, bias, cfg, need_x=True, need_k=True, need_b=True):
+    """The gradients a layer's autograd asks for, (d x, d kernel, d bias) with
+    hexconv2d_backward's contract, each on the fastest kernel it has
+    (hexconv2d_training_plan): d kernel / d bias through hexconv2d_weight_grad; d input of a
+    stride-2 layer as hexconv_transpose2d of gy with the layer's own kernel (a HexConv2d
+    kernel [O, C, 1, K] is the transposed layer's [in, out, 1, K]: no copy; the pad value never
+    reaches d input), otherwise hexconv2d_backward's d input."""
+    _abi.require_device(gy)
+    while x.dim() < 4:
+        x = x.unsqueeze(0)
+    x = x.contiguous()
+    dx = gk = gb = None
+    if need_k or (need_b and bias is not None):
+        gk, gb = hexconv2d_weight_grad(gy, x, kernel, bias, cfg, need_k, need_b)
+    if need_x:
+        B, C, h, w = (int(s) for s in x.shape)
+        kdt = kernel.dtype if kernel.dtype in (torch.float32, torch.float64) else torch.float32
+        route = "generic"
+        if x.dtype in _abi.TORCH_DTYPE:
+            route, _ = hexconv2d_training_plan(
+                x.dtype, kdt, B, C, int(kernel.shape[0]), h, w, cfg["r"], cfg["stride"],
+                cfg["pad"], cfg["dilation"], cfg["groups"], int(cfg["off"]), cfg["padding_mode"])
+        if route == "convt_s2":
+            dx = hexconv_transpose2d(gy.detach().to(kdt), kernel, None, cfg["off"], cfg["r"], 2,
+                                     cfg["pad"], 1, 1, output_size=(h, w), out_dtype=x.dtype)
+        else:
+            dx = hexconv2d_backward(gy, x, kernel, bias, cfg, True, False, False)[0]
+    return dx, gk, gb
+
+
 def hexconv2d_forward_plan(x_dtype, w_dtype, y_dtype, batch, in_channels, out_channels, h, w,
                            radius, stride=1, padding=0, dilation=1, groups=1, even_odd_offset=0,
                            padding_mode="constant", padding_value=0.0):

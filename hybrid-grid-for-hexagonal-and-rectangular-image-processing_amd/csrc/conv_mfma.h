@@ -23,7 +23,7 @@ constexpr int CM_CST = CM_PR * CM_PP;       // P channel stride
 constexpr int CM_WST = 7 * CM_OMAX + 16;    // weight channel stride (= 16 mod 32 banks)
 
 
-// Stride 2 (forward only): a workgroup's 4 x 64 outputs read staged rows 2 r0 .. 2 r0 + 8 and
+// Stride 2 (forward, and the d kernel GEMM of conv_mfma_bwd.hip): a workgroup's 4 x 64 outputs read staged rows 2 r0 .. 2 r0 + 8 and
 // staged columns 2 q0 + mink + (0..129).  Each staged row is kept as two column-parity planes:
 // sample column j sits in plane j & 1 at slot j >> 1, so the 16 columns 2 q + dk of a B fragment
 // (dk fixed within a tap and row parity) are 16 consecutive slots, as at stride 1.
@@ -120,6 +120,49 @@ __device__ __forceinline__ void cm_stage_p(float* __restrict__ ps, const Tin* __
                                        : (float)xb[((int64_t)c * G.h + yi) * G.w + xi];
             }
             ps[cc * CM_CST + pr * CM_PP + pc] = v;
+        }
+    }
+}
+
+// Where a wave's tap (dy, dk) starts in a staged P channel, in slots: stride 1 row wv + dy,
+// column dk; stride 2 row 2 wv + dy of the two column-parity planes (above): plane dk & 1,
+// slot dk >> 1.  The 16 columns of a fragment are the 16 slots from there.
+__device__ __forceinline__ int cs_slot(int row, int dk) {     // staged (row, column 2 q' + dk) at q' = 0
+    return row * CS_PP + (dk & 1) * CS_PL + (dk >> 1);
+}
+template <int S>
+__device__ __forceinline__ int cm_pslot(int wv, int dy, int dk) {
+    static_assert(S == 1 || S == 2, "stride");
+    return S == 1 ? (wv + dy) * CM_PP + dk : cs_slot(2 * wv + dy, dk);
+}
+
+// Stride 2: stage P rows 2 r0 .. 2 r0 + 8 (staged frame), columns 2 q0 + mink + (0..129), of
+// channels c0 .. c0+CC-1 as fp32 [c][row][plane][slot].  195 threads = 65 slots x 3 row phases;
+// a thread owns the two columns of its slot (their source indices computed once, cm_stage_p's
+// padding rules) and walks rows pr = phase, phase + 3, ... of every channel of the chunk.
+template <int CC, typename Tin>
+__device__ __forceinline__ void cs_stage_p(float* __restrict__ ps, const Tin* __restrict__ xb,
+                                           const MfmaGeom& G, int c0, int q0, int r0, int tid) {
+    if (tid < 3 * CS_SL) {
+        const int sl = tid % CS_SL, ph = tid / CS_SL;
+        const int px = 2 * q0 + G.mink + 2 * sl;          // plane 0's column; plane 1's is px + 1
+        const bool z0 = px >= G.Wp, z1 = px + 1 >= G.Wp;  // type1 structural zero columns
+        const int64_t x0 = z0 ? -1 : pad_map(px - G.ox, G.w, G.pad_mode);
+        const int64_t x1 = z1 ? -1 : pad_map(px + 1 - G.ox, G.w, G.pad_mode);
+#pragma unroll 4
+        for (int rr = ph; rr < CC * CS_PR; rr += 3) {
+            const int cc = rr / CS_PR, pr = rr - cc * CS_PR;
+            const int c = c0 + cc, py = 2 * r0 + pr;
+            float v0 = 0.f, v1 = 0.f;
+            if (c < G.C && py < G.Hp) {
+                const int64_t yi = pad_map(py - G.oy, G.h, G.pad_mode);
+                const int64_t row = ((int64_t)c * G.h + yi) * G.w;
+                if (!z0) v0 = (yi < 0 || x0 < 0) ? G.pad_value : (float)xb[row + x0];
+                if (!z1) v1 = (yi < 0 || x1 < 0) ? G.pad_value : (float)xb[row + x1];
+            }
+            float* const d = ps + cc * CS_CST + pr * CS_PP + sl;
+            d[0] = v0;
+            d[CS_PL] = v1;
         }
     }
 }

@@ -35,8 +35,8 @@ namespace hg {
 // (NOT / NQT tiles, channels per chunk CC, the transposed-D flag TD, the P slot's stride S).
 // k_hexconv_mfma_bf16, k_hexconv_mfma_s2 and k_hexconv_mfma_bf16_s2 are built from them, and
 // k_wsplit_bf16 from cb_split_w.  Not shared:
-//  * one-offs: the DMA issue lambdas, the two fp32 P stagers (cm_stage_p in conv_mfma.h,
-//    cs_stage_p) and the stride-2 bf16 P stager;
+//  * one-offs: the DMA issue lambdas, the two fp32 P stagers (cm_stage_p and cs_stage_p, both
+//    in conv_mfma.h for the backward kernels) and the stride-2 bf16 P stager;
 //  * the two MFMA loops (f32 and bf16): as force-inlined helpers they took a wave per SIMD from
 //    the NOT = 2 kernels (profiles/conv_mfma_refactor_resources.txt);
 //  * k_hexconv_mfma and k_hexconv_mfma_bf16d, which keep their own text throughout: built from
@@ -76,18 +76,6 @@ constexpr int CSB_PSZ = CS_PR * CS_PP + 1;  // ... at stride 2
 // stride 1, occupancy, not barrier count, is what the staging latency needs.
 constexpr int CS_CC = 4;
 static_assert(CS_CC % 4 == 0 && CS_CC <= CM_CC, "chunk: whole MFMA k quads, the weight stride's rows");
-
-// Where a wave's tap (dy, dk) starts in a staged P channel, in slots: stride 1 row wv + dy,
-// column dk; stride 2 row 2 wv + dy of the two column-parity planes (conv_mfma.h): plane
-// dk & 1, slot dk >> 1.  The 16 columns of a fragment are the 16 slots from there.
-__device__ __forceinline__ int cs_slot(int row, int dk) {     // staged (row, column 2 q' + dk) at q' = 0
-    return row * CS_PP + (dk & 1) * CS_PL + (dk >> 1);
-}
-template <int S>
-__device__ __forceinline__ int cm_pslot(int wv, int dy, int dk) {
-    static_assert(S == 1 || S == 2, "stride");
-    return S == 1 ? (wv + dy) * CM_PP + dk : cs_slot(2 * wv + dy, dk);
-}
 
 // Which tile of which image a workgroup computes, and this lane's place in the fragments.
 template <int NOT>
@@ -755,37 +743,7 @@ void k_hexconv_mfma_bf16d(const __bf16* __restrict__ x,
 // maps, the weight layouts, the accumulators and the epilogues are the stride-1 kernels'.
 // Sibling kernels, not a stride template argument: the stride-1 kernels keep their symbols.
 
-// Stage P rows 2 r0 .. 2 r0 + 8 (staged frame), columns 2 q0 + mink + (0..129), of channels
-// c0 .. c0+CS_CC-1 as fp32 [c][row][plane][slot].  195 threads = 65 slots x 3 row phases; a
-// thread owns the two columns of its slot (their source indices computed once, cm_stage_p's
-// padding rules) and walks rows pr = phase, phase + 3, ... of every channel of the chunk.
-template <typename Tin>
-__device__ __forceinline__ void cs_stage_p(float* __restrict__ ps, const Tin* __restrict__ xb,
-                                           const MfmaGeom& G, int c0, int q0, int r0, int tid) {
-    if (tid < 3 * CS_SL) {
-        const int sl = tid % CS_SL, ph = tid / CS_SL;
-        const int px = 2 * q0 + G.mink + 2 * sl;          // plane 0's column; plane 1's is px + 1
-        const bool z0 = px >= G.Wp, z1 = px + 1 >= G.Wp;  // type1 structural zero columns
-        const int64_t x0 = z0 ? -1 : pad_map(px - G.ox, G.w, G.pad_mode);
-        const int64_t x1 = z1 ? -1 : pad_map(px + 1 - G.ox, G.w, G.pad_mode);
-#pragma unroll 4
-        for (int rr = ph; rr < CS_CC * CS_PR; rr += 3) {
-            const int cc = rr / CS_PR, pr = rr - cc * CS_PR;
-            const int c = c0 + cc, py = 2 * r0 + pr;
-            float v0 = 0.f, v1 = 0.f;
-            if (c < G.C && py < G.Hp) {
-                const int64_t yi = pad_map(py - G.oy, G.h, G.pad_mode);
-                const int64_t row = ((int64_t)c * G.h + yi) * G.w;
-                if (!z0) v0 = (yi < 0 || x0 < 0) ? G.pad_value : (float)xb[row + x0];
-                if (!z1) v1 = (yi < 0 || x1 < 0) ? G.pad_value : (float)xb[row + x1];
-            }
-            float* const d = ps + cc * CS_CST + pr * CS_PP + sl;
-            d[0] = v0;
-            d[CS_PL] = v1;
-        }
-    }
-}
-
+// P is staged by cs_stage_p (conv_mfma.h) in chunks of CS_CC channels.
 template <typename Tin, typename Tout, int NOT>
 __global__ __launch_bounds__(CM_THREADS) void k_hexconv_mfma_s2(const Tin* __restrict__ x,
                                                                    const float* __restrict__ kern,
@@ -800,7 +758,7 @@ __global__ __launch_bounds__(CM_THREADS) void k_hexconv_mfma_s2(const Tin* __res
 
     const Tin* xb = x + K.b * (int64_t)G.C * G.h * G.w;
     for (int c0 = 0; c0 < G.C; c0 += CS_CC) {
-        cs_stage_p(ps, xb, G, c0, K.q0, K.r0, K.tid);
+        cs_stage_p<CS_CC>(ps, xb, G, c0, K.q0, K.r0, K.tid);
         cm_stage_w<CS_CC, NOT>(ws, kern, G, c0, K.o0, K.tid);
         __syncthreads();
         // ---- 7 taps x CS_CC / 4 channel quads x (NOT x 4) MFMAs ---------------------------

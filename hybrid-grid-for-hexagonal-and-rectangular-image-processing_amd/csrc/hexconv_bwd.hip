@@ -24,6 +24,7 @@
 
 #include "common.h"
 #include "hexconv_geom.h"
+#include "../../include/hygrid_train.h"
 
 namespace hg {
 
@@ -182,7 +183,10 @@ void conv_bwd_route(int x_dtype, int w_dtype, int64_t B, int64_t C, int64_t O, i
                     int dilation, int groups, int pad_mode, int* dx_kernel, int* dw_kernel);
 int conv_mfma_bwd_weight(const void* x, const float* gy, float* dk, float* db, int x_dtype,
                          int64_t B, int64_t C, int64_t O, int64_t h, int64_t w, int padding,
-                         int off, int pad_mode, double pad_value, hipStream_t st);
+                         int off, int pad_mode, double pad_value, hipStream_t st, int stride);
+int conv_wgrad_route(int x_dtype, int w_dtype, int64_t B, int64_t C, int64_t O, int64_t h,
+                     int64_t w, int64_t ho, int64_t wo, int radius, int stride, int padding,
+                     int dilation, int groups, int pad_mode);
 int conv_mfma_bwd_input(const float* kern, const float* gy, void* dx, int x_dtype, int64_t B,
                         int64_t C, int64_t O, int64_t h, int64_t w, int64_t ho, int64_t wo,
                         int padding, int off, hipStream_t st);
@@ -197,6 +201,33 @@ static int bwd_check(int64_t batch, int64_t C, int64_t O, int64_t h, int64_t w, 
     if (st) return st;
     if (3 * radius * radius - 3 * radius + 1 > BW_MAXK) return HG_EUNSUP;
     if (w_dtype != HG_F32 && w_dtype != HG_F64) return HG_EDTYPE;
+    return HG_OK;
+}
+
+// The rest of the geometry of a checked call (ho, wo are bwd_check's)
+static void bwd_fill(BwdGeom& G, int64_t batch, int64_t C, int64_t O, int64_t h, int64_t w,
+                     int radius, int stride, int padding, int dilation, int groups,
+                     int even_odd_offset, int pad_mode, double pad_value) {
+    G.B = batch; G.C = C; G.O = O; G.h = h; G.w = w;
+    G.r = radius; G.s = stride; G.p = padding; G.d = dilation;
+    G.K = 3 * radius * radius - 3 * radius + 1;
+    G.cg = (int)(C / groups);
+    G.og = (int)(O / groups);
+    G.op = ((even_odd_offset & 1) + padding) & 1;
+    G.pad_mode = pad_mode;
+    G.pad_value = pad_value;
+}
+
+// A call with no samples: zero gradients (the reference's empty sums)
+static int bwd_empty(void* dx, void* dkernel, void* dbias, int x_dtype, int w_dtype, int64_t batch,
+                     int64_t C, int64_t O, int64_t h, int64_t w, int groups, int K, hipStream_t s0) {
+    const size_t ws = w_dtype == HG_F64 ? 8 : 4;
+    if (dkernel && hipMemsetAsync(dkernel, 0, ws * (size_t)(O * (C / groups) * K), s0))
+        return HG_EINVAL;
+    if (dbias && hipMemsetAsync(dbias, 0, ws * (size_t)O, s0)) return HG_EINVAL;
+    if (dx && batch > 0 && h * w > 0 &&
+        hipMemsetAsync(dx, 0, (size_t)dtype_size(x_dtype) * (size_t)(batch * C * h * w), s0))
+        return HG_EINVAL;
     return HG_OK;
 }
 
@@ -254,27 +285,13 @@ extern "C" int hg_hexconv2d_backward(const void* x, const void* kernel, const vo
     if (st) return st;
     G.K = 3 * radius * radius - 3 * radius + 1;
     if (dx && !dtype_is_float(x_dtype)) return HG_EDTYPE;
-    if (batch == 0 || G.ho == 0 || G.wo == 0) {
-        // no samples: zero gradients (the reference's empty sums)
-        hipStream_t s0 = reinterpret_cast<hipStream_t>(stream);
-        const size_t ws = w_dtype == HG_F64 ? 8 : 4;
-        if (dkernel && hipMemsetAsync(dkernel, 0, ws * (size_t)(out_channels * (in_channels / groups) * G.K), s0))
-            return HG_EINVAL;
-        if (dbias && hipMemsetAsync(dbias, 0, ws * (size_t)out_channels, s0)) return HG_EINVAL;
-        if (dx && batch > 0 && h * w > 0 &&
-            hipMemsetAsync(dx, 0, (size_t)dtype_size(x_dtype) * (size_t)(batch * in_channels * h * w), s0))
-            return HG_EINVAL;
-        return HG_OK;
-    }
+    if (batch == 0 || G.ho == 0 || G.wo == 0)
+        return bwd_empty(dx, dkernel, dbias, x_dtype, w_dtype, batch, in_channels, out_channels, h,
+                         w, groups, G.K, reinterpret_cast<hipStream_t>(stream));
     if (!gy || (dx && !kernel) || (dkernel && !x)) return HG_EINVAL;
     if (!dx && !dkernel && !dbias) return HG_OK;
-    G.B = batch; G.C = in_channels; G.O = out_channels; G.h = h; G.w = w;
-    G.r = radius; G.s = stride; G.p = padding; G.d = dilation;
-    G.cg = (int)(in_channels / groups);
-    G.og = (int)(out_channels / groups);
-    G.op = ((even_odd_offset & 1) + padding) & 1;
-    G.pad_mode = pad_mode;
-    G.pad_value = pad_value;
+    bwd_fill(G, batch, in_channels, out_channels, h, w, radius, stride, padding, dilation, groups,
+             even_odd_offset, pad_mode, pad_value);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     // wide dense radius-2 layers: each gradient on its matrix-core kernel where it has one
     int dxk, dwk;
@@ -290,7 +307,7 @@ extern "C" int hg_hexconv2d_backward(const void* x, const void* kernel, const vo
     if (dkernel && dwk == HG_CONV_BWD_MFMA) {
         const int rc = conv_mfma_bwd_weight(x, (const float*)gy, (float*)dkernel, (float*)dbias,
                                             x_dtype, batch, in_channels, out_channels, h, w,
-                                            padding, even_odd_offset & 1, pad_mode, pad_value, s);
+                                            padding, even_odd_offset & 1, pad_mode, pad_value, s, 1);
         if (rc) return rc;
         dkernel = dbias = nullptr;
     }
@@ -317,5 +334,59 @@ extern "C" int hg_hexconv2d_backward_plan(int x_dtype, int w_dtype, int64_t batc
     if (dtype_size(x_dtype) == 0) return HG_EDTYPE;
     conv_bwd_route(x_dtype, w_dtype, batch, in_channels, out_channels, h, w, ho, wo, radius,
                    stride, padding, dilation, groups, pad_mode, dx_kernel, dw_kernel);
+    return HG_OK;
+}
+
+// ---- hygrid_train.h ----------------------------------------------------------------------------
+extern "C" int hg_hexconv2d_weight_grad(const void* x, const void* gy, void* dkernel, void* dbias,
+                                        int x_dtype, int w_dtype, int64_t batch,
+                                        int64_t in_channels, int64_t out_channels, int64_t h,
+                                        int64_t w, int radius, int stride, int padding,
+                                        int dilation, int groups, int even_odd_offset,
+                                        int pad_mode, double pad_value, void* stream) {
+    using namespace hg;
+    BwdGeom G;
+    const int st = bwd_check(batch, in_channels, out_channels, h, w, radius, stride, padding,
+                             dilation, groups, pad_mode, w_dtype, &G.ho, &G.wo);
+    if (st) return st;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (batch == 0 || G.ho == 0 || G.wo == 0)
+        return bwd_empty(nullptr, dkernel, dbias, x_dtype, w_dtype, batch, in_channels,
+                         out_channels, h, w, groups, 3 * radius * radius - 3 * radius + 1, s);
+    if (!gy || (dkernel && !x)) return HG_EINVAL;
+    if (!dkernel && !dbias) return HG_OK;
+    bwd_fill(G, batch, in_channels, out_channels, h, w, radius, stride, padding, dilation, groups,
+             even_odd_offset, pad_mode, pad_value);
+    // the matrix-core GEMM sums d bias beside d kernel; d bias alone is one generic pass
+    const int route = conv_wgrad_route(x_dtype, w_dtype, batch, in_channels, out_channels, h, w,
+                                       G.ho, G.wo, radius, stride, padding, dilation, groups,
+                                       pad_mode);
+    if (dkernel && route != HG_CONV_WGRAD_GENERIC)
+        return conv_mfma_bwd_weight(x, (const float*)gy, (float*)dkernel, (float*)dbias, x_dtype,
+                                    batch, in_channels, out_channels, h, w, padding,
+                                    even_odd_offset & 1, pad_mode, pad_value, s,
+                                    route == HG_CONV_WGRAD_MFMA_S2 ? 2 : 1);
+    if (w_dtype == HG_F64) {
+        HG_DISPATCH_IN(x_dtype, TX, { return bwd_launch<TX, double>(x, nullptr, gy, nullptr, dkernel, dbias, G, s); });
+    } else {
+        HG_DISPATCH_IN(x_dtype, TX, { return bwd_launch<TX, float>(x, nullptr, gy, nullptr, dkernel, dbias, G, s); });
+    }
+    return HG_EDTYPE;
+}
+
+extern "C" int hg_hexconv2d_weight_grad_plan(int x_dtype, int w_dtype, int64_t batch,
+                                             int64_t in_channels, int64_t out_channels, int64_t h,
+                                             int64_t w, int radius, int stride, int padding,
+                                             int dilation, int groups, int pad_mode,
+                                             hg_host_int_out kernel) {
+    using namespace hg;
+    if (!kernel) return HG_EINVAL;
+    int64_t ho, wo;
+    const int st = bwd_check(batch, in_channels, out_channels, h, w, radius, stride, padding,
+                             dilation, groups, pad_mode, w_dtype, &ho, &wo);
+    if (st) return st;
+    if (dtype_size(x_dtype) == 0) return HG_EDTYPE;
+    *kernel = conv_wgrad_route(x_dtype, w_dtype, batch, in_channels, out_channels, h, w, ho, wo,
+                               radius, stride, padding, dilation, groups, pad_mode);
     return HG_OK;
 }
